@@ -7,8 +7,13 @@ wavefront, inputs and outputs resident in HBM when the timed region starts.  A "
 of pzg_decompress_many over the whole batch.  N>1: one process per GPU, every rank decodes its own
 65,536-stream shard of an N x 65,536 batch (weak scaling, no data-path collective).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the headline.  --full adds everything else this file
+measures or checks: every stream of the timed batch verified on one more step, the 32 KiB LDS-ring variant, the other
+BASELINE configs, the host-buffer and incremental paths, the CPU baselines and the Adler-32 microbench.
+--dump-outputs DIR writes what the last timed step computed as DIR/*.npy (see dump_outputs).
 
 Prints ONE JSON line on rank 0.
 """
@@ -92,42 +97,75 @@ def hetero_blob(seed):
     return t, zlib.compress(t, level)
 
 
+def pool_blob(args, seed):
+    """The (text, zlib stream) pair of pool seed `seed`: a function of the arguments and the seed alone."""
+    if args.workload == "fixed_4k":
+        t = corpus.zipf_text(4096, seed)
+        co = zlib.compressobj(1, zlib.DEFLATED, 15, 8, zlib.Z_FIXED)
+        z = co.compress(t) + co.flush()
+    elif args.workload == "skewed_bytes":  # literal-heavy, many codes longer than the primary table
+        t = corpus.skewed_bytes(args.blob_bytes, seed)
+        z = zlib.compress(t, args.level)
+    elif args.workload == "fixed_bin":  # fixed-Huffman blocks whose literals are all >= 144: 9-bit codes
+        t = bytes(b | 0x80 for b in corpus.zipf_text(4096, seed))
+        co = zlib.compressobj(1, zlib.DEFLATED, 15, 8, zlib.Z_FIXED)
+        z = co.compress(t) + co.flush()
+    elif args.workload == "runs":  # overlapping matches: byte runs and short repeating patterns (dist < len)
+        t = corpus.mixed_data(args.blob_bytes, 2 + (seed & 1) + 4 * seed)
+        z = zlib.compress(t, args.level)
+    elif args.workload == "html":  # slices of the reference's own RFC html fixtures
+        t = corpus.html_slice(args.blob_bytes, seed)
+        z = zlib.compress(t, args.level)
+    elif args.workload == "mixed":
+        size = 1024 * (1 + (seed * 2654435761 >> 7) % 64)
+        t = corpus.zipf_text(size, seed)
+        z = zlib.compress(t, 6)
+    elif args.workload == "hetero":
+        t, z = hetero_blob(seed)
+    else:
+        t = corpus.zipf_text(args.blob_bytes, seed)
+        z = zlib.compress(t, args.level)
+    if args.gzip:  # same DEFLATE body, gzip header and CRC-32 + ISIZE trailer instead of the zlib ones
+        import struct
+        z = b"\x1f\x8b\x08\x00\x00\x00\x00\x00\x00\x03" + z[2:-4] + struct.pack("<II", zlib.crc32(t), len(t) & 0xffffffff)
+    return t, z
+
+
 def build_pool(args):
-    """P distinct (text, zlib stream) pairs, seeds 0..P-1, identical on every rank."""
-    texts, zs = [], []
-    for seed in range(args.pool):
-        if args.workload == "fixed_4k":
-            t = corpus.zipf_text(4096, seed)
-            co = zlib.compressobj(1, zlib.DEFLATED, 15, 8, zlib.Z_FIXED)
-            z = co.compress(t) + co.flush()
-        elif args.workload == "skewed_bytes":  # literal-heavy, many codes longer than the primary table
-            t = corpus.skewed_bytes(args.blob_bytes, seed)
-            z = zlib.compress(t, args.level)
-        elif args.workload == "fixed_bin":  # fixed-Huffman blocks whose literals are all >= 144: 9-bit codes
-            t = bytes(b | 0x80 for b in corpus.zipf_text(4096, seed))
-            co = zlib.compressobj(1, zlib.DEFLATED, 15, 8, zlib.Z_FIXED)
-            z = co.compress(t) + co.flush()
-        elif args.workload == "runs":  # overlapping matches: byte runs and short repeating patterns (dist < len)
-            t = corpus.mixed_data(args.blob_bytes, 2 + (seed & 1) + 4 * seed)
-            z = zlib.compress(t, args.level)
-        elif args.workload == "html":  # slices of the reference's own RFC html fixtures
-            t = corpus.html_slice(args.blob_bytes, seed)
-            z = zlib.compress(t, args.level)
-        elif args.workload == "mixed":
-            size = 1024 * (1 + (seed * 2654435761 >> 7) % 64)
-            t = corpus.zipf_text(size, seed)
-            z = zlib.compress(t, 6)
-        elif args.workload == "hetero":
-            t, z = hetero_blob(seed)
-        else:
-            t = corpus.zipf_text(args.blob_bytes, seed)
-            z = zlib.compress(t, args.level)
-        if args.gzip:  # same DEFLATE body, gzip header and CRC-32 + ISIZE trailer instead of the zlib ones
-            import struct
-            z = b"\x1f\x8b\x08\x00\x00\x00\x00\x00\x00\x03" + z[2:-4] + struct.pack("<II", zlib.crc32(t), len(t) & 0xffffffff)
-        texts.append(t)
-        zs.append(z)
-    return texts, zs
+    """P distinct (text, zlib stream) pairs, seeds 0..P-1, identical on every rank.  Built on up to 16 threads (zlib and
+    numpy release the GIL; 8,192 level-6 compressions take ~11 s of one core), in seed order whatever the thread count."""
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(max(1, min(16, os.cpu_count() or 1))) as ex:
+        pairs = list(ex.map(lambda seed: pool_blob(args, seed), range(args.pool)))
+    return [p[0] for p in pairs], [p[1] for p in pairs]
+
+
+def dump_outputs(path, n, out_off, out_cap, d_out, d_status, d_out_len, d_in_used, d_adler):
+    """--dump-outputs: what the caller of the timed step receives, from its last step, as float64 / float32 .npy files that
+    two builds can be compared by (the inputs are a function of the arguments).  Per stream, for every stream of the batch
+    or a seeded sample of 65,536 (`streams`): `status`, `out_len`, `in_used` and `checksum` (the Adler-32, or the CRC-32 with
+    --gzip).  The decoded bytes of a seeded sample of streams (`byte_streams`, in that order), each stream's whole extent,
+    cut at 8 MiB in all: `bytes` (float32).  32 MiB + 2.5 MiB at most.  (detail[] is left out: unspecified on success.)"""
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(0xD0D0)
+    rows = np.arange(n) if n <= 65536 else np.sort(rng.choice(n, 65536, replace=False))
+    rows_d = torch.from_numpy(rows).to(d_out.device)
+    per_stream = lambda d, np_type: d[rows_d].cpu().numpy().view(np_type).astype(np.float64)  # noqa: E731
+    arrays = {"streams": rows.astype(np.float64), "status": per_stream(d_status, np.int32), "out_len": per_stream(d_out_len, np.int64),
+              "in_used": per_stream(d_in_used, np.int64), "checksum": per_stream(d_adler, np.uint32)}
+    budget, picked, pieces = 8 << 20, [], []
+    for k in rng.permutation(n):
+        if budget == 0:
+            break
+        take = min(int(out_cap[k]), budget)
+        pieces.append(d_out[int(out_off[k]):int(out_off[k]) + take])
+        picked.append(k)
+        budget -= take
+    arrays["byte_streams"] = np.array(picked, dtype=np.float64)
+    arrays["bytes"] = torch.cat(pieces).cpu().numpy().astype(np.float32)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return sum(a.nbytes for a in arrays.values())
 
 
 def main():
@@ -151,7 +189,12 @@ def main():
     ap.add_argument("--no-host-path", action="store_true", help="skip the host-buffer (PCIe-inclusive) measurement")
     ap.add_argument("--no-variants", action="store_true", help="skip the config 3 / config 5 share / 64 KiB legs of the default run")
     ap.add_argument("--incremental-decoders", type=int, default=4096, help="decoders of the incremental-path leg (pzg_decoder_feed, 32 KiB pieces); 0 = skip")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: verify every stream, and run the variants, host-path, incremental, CPU-baseline and Adler-32 legs "
+                         "(the options above that skip or size those legs apply only here)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/*.npy (rank 0's shard when --gpus > 1)")
     args = ap.parse_args()
+    verify = args.full and not args.no_verify
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -271,6 +314,9 @@ def main():
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0  # this rank's K steps, between a barrier + synchronize in front and a synchronize behind
     barrier()
+    if args.dump_outputs and rank == 0:
+        nb_dump = dump_outputs(args.dump_outputs, n, out_off, out_cap, d_out, d_status, d_out_len, d_in_used, d_adler)
+        log(f"[bench] {nb_dump / 2**20:.1f} MiB of outputs written to {args.dump_outputs}")
     per_rank = None
     if world > 1:
         # the job's time is the slowest rank's (MAX); every rank's own wall time, kernel time and share are reported beside it
@@ -293,7 +339,7 @@ def main():
     # what gets verified: a step that did nothing cannot pass on what an earlier one left behind.  Its kernel time (HIP
     # events) is reported beside the timed steps': the same work takes the same time.
     verify_ms = None
-    if not args.no_verify:
+    if verify:
         d_out.fill_(0xCD)
         d_status.fill_(-1)
         d_out_len.zero_()
@@ -307,7 +353,7 @@ def main():
     out_len = d_out_len.cpu().numpy()
     adler = d_adler.cpu().numpy().view(np.uint32)
     bit_exact = None
-    if not args.no_verify:
+    if verify:
         exp_adler = np.array([(zlib.crc32(t) if args.gzip else zlib.adler32(t)) for t in texts], dtype=np.uint32)[pick]
         ok = bool((status == 0).all() and (out_len == out_cap).all() and (adler == exp_adler).all()
                   and (d_in_used.cpu().numpy() == in_len).all())
@@ -337,7 +383,7 @@ def main():
 
     # ---- A/B evidence: the same batch through the pure 32 KiB LDS-ring variant (north_star's literal design) ----
     ab = None
-    if rank == 0 and world == 1 and not args.no_ab and ring_bits != 15:
+    if rank == 0 and world == 1 and args.full and not args.no_ab and ring_bits != 15:
         ctx.set_ring_bits(15)
         step()
         torch.cuda.synchronize()
@@ -345,7 +391,7 @@ def main():
         for _ in range(2):
             step()
             ms15.append(ctx.last_kernel_ms())
-        ok15 = bool((d_status.cpu().numpy() == 0).all() and (d_adler.cpu().numpy().view(np.uint32) == exp_adler).all()) if not args.no_verify else None
+        ok15 = bool((d_status.cpu().numpy() == 0).all() and (d_adler.cpu().numpy().view(np.uint32) == exp_adler).all()) if verify else None
         ab = {"ring_bits": 15, "kernel_ms": round(float(np.mean(ms15)), 3),
               "GiBps": round(int(out_cap.sum()) / (float(np.mean(ms15)) * 1e-3) / 2**30, 2), "bit_exact": ok15,
               "note": "whole DEFLATE window as an LDS ring: 4 stream-waves per CU (LDS-bound occupancy)"}
@@ -405,7 +451,8 @@ def main():
                            "group; a stream's first span is cut into strips of equal WORK by the wave's profile of the stream before it (checked by "
                            "the run-ups); 128-bit windows for stream tails and short streams"),
                 "verified": ("every stream: status, length, in_used, Adler-32 and full byte compare, on one more step run after the "
-                             "timed region over POISONED output / status arrays") if bit_exact is not None else "skipped",
+                             "timed region over POISONED output / status arrays") if bit_exact is not None else
+                            "skipped" if args.full else "not in a plain run (--full verifies every stream)",
             },
             "roofline": {
                 "bound": "hbm",
@@ -434,7 +481,7 @@ def main():
     # ---- BASELINE configs 3 and 5 and the 64 KiB batch of SURVEY.md 8d in the same run: one launch each over
     # arenas resident in HBM, three timed launches (HIP events), every stream verified (status, length, in_used, Adler-32, every
     # byte) on a run over poisoned outputs; each with its own algorithmic bytes and roofline fraction.
-    if rank == 0 and world == 1 and not args.no_variants and args.workload == "l6_32k":
+    if rank == 0 and world == 1 and args.full and not args.no_variants and args.workload == "l6_32k":
         from devbatch import DeviceBatch
 
         def variant(name, what, texts_v, zs_v, count, seed, profile=None):
@@ -498,7 +545,7 @@ def main():
 
     # ---- the same batch handed over as HOST buffers (what a `decompress` caller pays): staging + H2D + kernel + D2H.
     # Reported beside `value`, never as `value` (which is measured with the arenas resident in HBM).
-    if rank == 0 and world == 1 and not args.no_host_path:
+    if rank == 0 and world == 1 and args.full and not args.no_host_path:
         h_out = np.empty(int(d_out.numel()), dtype=np.uint8)
         ctx.decompress_many_raw(h_in, in_off, in_len, h_out, out_off, out_cap)  # warm the staging buffers
 
@@ -514,7 +561,7 @@ def main():
 
         h_out[:] = 0xCD  # poisoned, then a call whose results are verified: EVERY stream's status, length and bytes
         o_len, o_st, _det, _used, _ad = ctx.decompress_many_raw(h_in, in_off, in_len, h_out, out_off, out_cap)
-        ok_h = bool((o_st == 0).all() and (o_len == out_cap).all()) and (args.no_verify or every_stream_equal(h_out))
+        ok_h = bool((o_st == 0).all() and (o_len == out_cap).all()) and (not verify or every_stream_equal(h_out))
         dts = []
         for _ in range(5):  # (median of five calls, every sample listed: VERDICT r4 item 5)
             t0h = time.perf_counter()
@@ -539,7 +586,7 @@ def main():
             ctx.decompress_many_raw(p_in.a, in_off, in_len, p_out.a, out_off, out_cap, pinned=True)  # allocates the device mirrors
             p_out.a[:] = 0xCD  # poisoned, then a call whose results are verified ...
             o_len, o_st, _det, _used, o_ad = ctx.decompress_many_raw(p_in.a, in_off, in_len, p_out.a, out_off, out_cap, pinned=True)
-            ok_p = bool((o_st == 0).all() and (o_len == out_cap).all() and (o_ad == exp_adler).all()) if not args.no_verify else None
+            ok_p = bool((o_st == 0).all() and (o_len == out_cap).all() and (o_ad == exp_adler).all()) if verify else None
             if ok_p:
                 ok_p = every_stream_equal(p_out.a)
             dtps = []
@@ -563,7 +610,7 @@ def main():
 
     # ---- the incremental path (Benchmark.hs:53-70): 4,096 resumable decoders fed 32 KiB pieces,
     # host buffers both ways, one launch per feed call.  Reported beside `value`, never as it.
-    if rank == 0 and world == 1 and args.incremental_decoders > 0 and not args.no_host_path:
+    if rank == 0 and world == 1 and args.full and args.incremental_decoders > 0 and not args.no_host_path:
         from pure_zlib_amd import benchmark as HB
         inc_plain = [corpus.zipf_text(256 * 1024, 7000 + k) for k in range(32)]
         inc_z = [zlib.compress(t, 6) for t in inc_plain]
@@ -575,7 +622,7 @@ def main():
     # ---- CPU baseline, rank 0 at N=1 only: the oracle ("port": the bit-at-a-time restatement of pure-zlib) and system
     # zlib, on this box's host cores.  All cores: the WHOLE timed batch.  One thread: a bounded sample of it (the whole
     # batch would take most of a minute per decoder).  A reported baseline, not a target.
-    if rank == 0 and world == 1 and args.cpu_sample > 0:
+    if rank == 0 and world == 1 and args.full and args.cpu_sample > 0:
         from oracle import oracle as O
         L = O.lib()
         cores = os.cpu_count() or 1
@@ -625,7 +672,7 @@ def main():
         # all cores: the box may hand this process less than its logical CPU count (quota), so a few thread counts are
         # tried on the whole batch and the best one is what is reported, with its thread count
         best = None
-        gpu_vs_port = not args.no_verify and not args.gzip
+        gpu_vs_port = verify and not args.gzip
         for th in sorted({nthreads, max(1, nthreads // 2), max(1, nthreads // 4), min(nthreads, 32), min(nthreads, 16)}, reverse=True):
             nb_o, dt_o = timed(L.pzo_decompress_many_mt, n, th)
             # GPU output against the restatement on EVERY stream of the timed batch -- the oracle's per-stream
@@ -667,7 +714,7 @@ def main():
         }
 
     # ---- BASELINE config 2: Adler-32 over one large buffer (HBM-bound microbench) -------------------
-    if rank == 0 and world == 1 and args.adler_gib > 0:
+    if rank == 0 and world == 1 and args.full and args.adler_gib > 0:
         nb = int(args.adler_gib * 2**30)
         free, _tot = torch.cuda.mem_get_info()
         nb = min(nb, int(free * 0.8))

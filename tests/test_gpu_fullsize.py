@@ -146,7 +146,7 @@ def _bench_two_ranks(extra):
                PZG_BENCH_DEVICE="0", PZG_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--pool", "256"] + extra
+           "--pool", "256", "--full"] + extra
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -179,6 +179,36 @@ def test_bench_py_config5_command_two_ranks():
     assert 14000 < r["config"]["streams_per_gpu"] < 19000 and r["config"]["parallelism"] == "shard2"  # (balanced by bytes, not by count)
     assert "config 5" in r["config"]["workload"] and r["value"] > 0
     assert sum(r["per_rank"]["streams"]) == 2 * 16384 and 1.0 <= r["per_rank"]["shard_imbalance"] < 1.05
+
+
+def test_bench_py_plain_run_dumps_what_its_last_step_computed(tmp_path):
+    """A plain bench.py run times the headline alone (--steps timed steps, no verification, none of --full's legs), and
+    --dump-outputs holds what its last timed step computed: every stream's status / length / in_used / Adler-32 and the
+    sampled streams' bytes, against the plaintexts of the same seeded batch."""
+    import argparse
+    import bench
+    from pure_zlib_amd.shard import plan_shards
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--pool", "256",
+           "--streams", "4096", "--dump-outputs", str(tmp_path)]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    r = json.loads(lines[0])
+    assert r["steps"] == 3 and r["bit_exact"] is None and r["config"]["streams_per_gpu"] == 4096
+    assert abs(r["value"] - 4096 * 32768 / (r["ms_per_step"] * 1e-3) / 2**30) / r["value"] < 0.02
+    for leg in ("lds_ring_32k_variant", "fixed_4k_variant", "host_buffers_variant", "incremental_variant", "cpu_baseline", "adler32_microbench"):
+        assert leg not in r, leg
+    texts, zs = bench.build_pool(argparse.Namespace(workload="l6_32k", pool=256, blob_bytes=32768, level=6, gzip=False))
+    perm = np.random.default_rng(0xB00C).integers(0, len(zs), size=4096)
+    pick = perm[plan_shards(np.array([len(t) for t in texts], dtype=np.int64)[perm], 1)[0]]
+    d = {f[:-4]: np.load(os.path.join(tmp_path, f)) for f in os.listdir(tmp_path)}
+    assert all(a.dtype in (np.float32, np.float64) for a in d.values()) and sum(a.nbytes for a in d.values()) <= 64 << 20
+    assert np.array_equal(d["streams"], np.arange(4096)) and (d["status"] == 0).all() and (d["out_len"] == 32768).all()
+    assert np.array_equal(d["in_used"], [len(zs[k]) for k in pick])
+    assert np.array_equal(d["checksum"], [zlib.adler32(texts[k]) for k in pick])
+    want = b"".join(texts[pick[int(k)]] for k in d["byte_streams"])
+    assert len(d["byte_streams"]) == 256 and np.array_equal(d["bytes"], np.frombuffer(want, dtype=np.uint8))
 
 
 def test_adler32_over_one_16_gib_device_buffer(gpu_ctx):

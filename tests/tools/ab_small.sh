@@ -5,7 +5,7 @@ cd "$(dirname "$0")/../.."
 run() { # lib args...
   lib=$1; shift
   if [ "$lib" = product ]; then unset PZG_LIB; else export PZG_LIB=$lib; fi
-  timeout 300 python bench.py "$@" --no-ab --no-host-path --no-variants --adler-gib 0 --cpu-sample 0 --incremental-decoders 0 --steps 5 --warmup 3 2>/dev/null | tail -1 | python -c "import json,sys;d=json.loads(sys.stdin.read());print('$lib', '$*', d['value'], d['ms_per_step'], d['bit_exact'])"
+  timeout 300 python bench.py --full "$@" --no-ab --no-host-path --no-variants --adler-gib 0 --cpu-sample 0 --incremental-decoders 0 --steps 5 --warmup 3 2>/dev/null | tail -1 | python -c "import json,sys;d=json.loads(sys.stdin.read());print('$lib', '$*', d['value'], d['ms_per_step'], d['bit_exact'])"
 }
 for lib in ${LIBS:-product}; do
   run $lib --workload l6_32k --streams 1048576 --blob-bytes 2048 --pool 4096

@@ -9,7 +9,7 @@ cd /tmp; export TMPDIR=/tmp
 tag=r04_final
 sections=${*:-bench stats traffic sq sweeps}
 has() { [[ " $sections " == *" $1 "* ]]; }
-if has bench; then python3 $root/bench.py > $out/${tag}_bench.json 2> $out/${tag}_bench.err; fi
+if has bench; then python3 $root/bench.py --full > $out/${tag}_bench.json 2> $out/${tag}_bench.err; fi
 if has stats; then
   rm -rf /tmp/ks; timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks -o ks -- python3 $root/bench.py --cpu-sample 0 --no-ab --no-host-path --no-variants > /tmp/ks.log 2>&1
   cp $(find /tmp/ks -name "*kernel_stats.csv" | head -1) $out/${tag}_kernel_stats.csv
@@ -51,7 +51,7 @@ if has sq; then
 fi
 if has sweeps; then
   : > $out/${tag}_sweeps.txt
-  line() { python3 $root/bench.py --steps 8 --warmup 2 --no-host-path --no-variants --cpu-sample 0 --adler-gib 0 --no-ab "$@" 2>/dev/null | python3 -c "
+  line() { python3 $root/bench.py --full --steps 8 --warmup 2 --no-host-path --no-variants --cpu-sample 0 --adler-gib 0 --no-ab "$@" 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read()); print(' '.join(sys.argv[1:]), '->', d['value'], 'GiB/s kernel_ms', d['roofline']['kernel_ms_avg'], 'bit_exact', d['bit_exact'])" "$@" >> $out/${tag}_sweeps.txt; }
   for wl in fixed_4k mixed html skewed_bytes fixed_bin runs; do line --workload $wl; done

@@ -8,7 +8,7 @@ cd /tmp; export TMPDIR=/tmp
 tag=r06_final
 sections=${*:-bench stats traffic sq sweeps}
 has() { [[ " $sections " == *" $1 "* ]]; }
-if has bench; then python3 $root/bench.py > $out/${tag}_bench.json 2> $out/${tag}_bench.err; fi
+if has bench; then python3 $root/bench.py --full > $out/${tag}_bench.json 2> $out/${tag}_bench.err; fi
 if has stats; then
   rm -rf /tmp/ks; timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks -o ks -- python3 $root/bench.py --cpu-sample 0 --no-ab --no-host-path --no-variants --adler-gib 0 > /tmp/ks.log 2>&1
   cp $(find /tmp/ks -name "*kernel_stats.csv" | head -1) $out/${tag}_kernel_stats.csv

@@ -14,7 +14,7 @@ for wl in "l6_32k:--workload l6_32k" "mixed:--workload mixed --streams 131072"; 
   base=
   for n in 1 2 4 8; do
     [ "$n" -gt "$ndev" ] && continue
-    common="--gpus $n --steps $steps --warmup $warm --no-ab --no-host-path --no-variants --cpu-sample 0 --adler-gib 0 $args"
+    common="--gpus $n --full --steps $steps --warmup $warm --no-ab --no-host-path --no-variants --cpu-sample 0 --adler-gib 0 $args"
     if [ "$n" = 1 ]; then line=$(python3 $root/bench.py $common 2>/dev/null | tail -1)
     else line=$(python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $((29500 + n)) $root/bench.py $common 2>/dev/null | grep '^{' | tail -1); fi
     python3 - "$name" "$n" "$line" "$base" <<'PY'

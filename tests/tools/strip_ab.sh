@@ -6,7 +6,7 @@ for pass in $(seq 1 ${3:-2}); do
   for tag in prod $1; do
     lib=$PWD/build/exp/libpzg_$tag.so; [ $tag = prod ] && lib=$PWD/pure_zlib_amd/libpzg.so
     for wl in $wls; do
-      PZG_LIB=$lib timeout 300 python bench.py --workload $wl --steps 8 --warmup 2 --no-ab --no-host-path --no-variants --cpu-sample 0 --adler-gib 0 2>&1 | tail -1 |
+      PZG_LIB=$lib timeout 300 python bench.py --full --workload $wl --steps 8 --warmup 2 --no-ab --no-host-path --no-variants --cpu-sample 0 --adler-gib 0 2>&1 | tail -1 |
         python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$tag', '$wl', d['value'], d['bit_exact'])"
     done
   done

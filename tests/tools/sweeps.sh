@@ -3,7 +3,7 @@
 cd "$(dirname "$0")/../.."
 out=${1:-gpurun_out/sweeps.txt}; mkdir -p "$(dirname "$out")"; : > "$out"
 run() {
-  timeout 400 python bench.py --no-ab --no-host-path --no-variants --adler-gib 0 --cpu-sample 0 --incremental-decoders 0 --steps 5 "$@" 2>/dev/null | tail -1 |
+  timeout 400 python bench.py --full --no-ab --no-host-path --no-variants --adler-gib 0 --cpu-sample 0 --incremental-decoders 0 --steps 5 "$@" 2>/dev/null | tail -1 |
     python -c "import json,sys;d=json.loads(sys.stdin.read());print('$*', '->', d['value'], 'GiB/s kernel_ms', d.get('kernel_ms', d['ms_per_step']), 'bit_exact', d.get('bit_exact'))" | tee -a "$out"
 }
 run --workload fixed_4k
