@@ -216,8 +216,17 @@ PZG_API void  pzg_host_free(void *p);
  *   status[n]              PZG_OK or PZG_E_*
  *   detail[2n]             two detail words per stream (see the status table); may be NULL
  *   in_used[n]             input bytes consumed incl. the Adler trailer; may be NULL
- *   adler[n]               Adler-32 computed over the decoded bytes; may be NULL.  (Of a stream that failed: over what had been
- *                          decoded by then -- 0 if it had outgrown out_cap[i] by then: what lies past the capacity is not stored.)
+ *   adler[n]               Adler-32 computed over the decoded bytes; may be NULL.  With PZG_GZIP: the CRC-32 of them.
+ *
+ * A stream that FAILED (status neither PZG_OK nor PZG_E_OUT_TOO_SMALL) delivers what the reference had emitted before the error:
+ *   out_len[i]   those bytes -- nothing of a stored block whose bytes run out (Deflate.hs:77: nextBlock reads the block whole
+ *                before emitBlock emits it)
+ *   extent       bytes [0, min(out_len[i], out_cap[i])) are those bytes, on every path (device pointers, staged, PZG_HOST_PINNED,
+ *                sharded); nothing is written past out_cap[i]
+ *   adler[i]     the Adler-32 of those bytes, 0 if out_len[i] > out_cap[i] (what lies past the capacity is not stored).  With
+ *                PZG_GZIP: their CRC-32, or 0 if out_len[i] > out_cap[i]; a member whose CRC-32 or ISIZE is wrong but whose
+ *                output outgrew the capacity reports PZG_E_OUT_TOO_SMALL (nothing stored to check)
+ *   in_used[i]   unspecified
  *
  * Extents may be laid out with gaps (aligned arenas) and in any order; they must not overlap on the
  * output side.  One compressed stream may be up to 16 GiB (longer ones report PZG_E_TRUNCATED); the decoded size is

@@ -408,6 +408,16 @@ static void emit_past_chunk(dstate *s, uint32_t dist, uint32_t len)
 static void emit_stored(dstate *s, uint32_t len)
 {
     /* nextBlock is entered with dcsNextBitNo == 8 (nextWord16 leaves it there, :236-249) */
+    if (!s->ev_type) {
+        /* decompress (batch): Deflate.hs:77 is `emitBlock =<< nextBlock len` -- getBlock must have the whole block before
+         * anything is emitted, so a stored block the input cannot complete emits none of its bytes.  (The incremental
+         * trace keeps emitting as it reads: there the pieces that follow are the input still to come.) */
+        uint64_t have = (uint64_t)(s->pend - s->p);
+        uint32_t c;
+        for (c = s->chunk_next; c < s->nchunks && have < len; c++) have += s->coff[c + 1] - s->coff[c];
+        if (have < len)
+            raise_err(s, PZO_E_TRUNCATED, 0, 0, "Decompression error: Ran out of data mid-decompression 2.");
+    }
     ow_advance(s, len);
     for (;;) {
         uint64_t have = (uint64_t)(s->pend - s->p);

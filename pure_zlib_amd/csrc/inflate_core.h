@@ -4301,45 +4301,46 @@ struct Decoder {
         return ST_OK;
     }
 
+    // RFC 1952 2.2: a gzip file is a series of members; they are decoded one after the other into one output.
+    // Each member's ISIZE is checked here against what it produced; the CRC-32s are folded into the CRC the
+    // whole output must have (crc32_append), which crc32_verify_kernel then checks in one pass.
+    PZG_FN int gzip_members()
+    {
+        uint64_t mstart = 0;
+        gz_expect = 0;
+        for (;;) {
+            if (int st = gzip_header()) return st;
+            if (int st = blocks()) return st;
+            br.align_to_byte();
+            if (br.avail() < 64) return fail(ST_TRUNCATED, 0, 0);
+            const uint32_t crc = br.peek32();
+            br.drop(32);
+            const uint32_t isize = br.peek32();
+            br.drop(32);
+            const uint64_t mlen = op - mstart;
+            gz_expect = crc32_append(gz_expect, crc, mlen);
+            // (reported unless the CRC-32 is wrong as well: crc32_verify_kernel looks at that first, as zlib does)
+            if (isize != (uint32_t)mlen) return fail(ST_GZIP_ISIZE, isize, (uint32_t)mlen);
+            mstart = op;
+            if (br.avail() < 16 || (br.peek32() & 0xffffu) != 0x8b1fu) return ST_OK;  // no further member follows
+        }
+    }
+
     PZG_FN int decode()
     {
-        if (GZIP) {
-            // RFC 1952 2.2: a gzip file is a series of members; they are decoded one after the other into one output.
-            // Each member's ISIZE is checked here against what it produced; the CRC-32s are folded into the CRC the
-            // whole output must have (crc32_append), which crc32_verify_kernel then checks in one pass.
-            uint64_t mstart = 0;
-            gz_expect = 0;
-            for (;;) {
-                if (int st = gzip_header()) return st;
-                if (int st = blocks()) return st;
-                br.align_to_byte();
-                if (br.avail() < 64) return fail(ST_TRUNCATED, 0, 0);
-                const uint32_t crc = br.peek32();
-                br.drop(32);
-                const uint32_t isize = br.peek32();
-                br.drop(32);
-                const uint64_t mlen = op - mstart;
-                gz_expect = crc32_append(gz_expect, crc, mlen);
-                // (reported unless the CRC-32 is wrong as well: crc32_verify_kernel looks at that first, as zlib does)
-                if (isize != (uint32_t)mlen) {
-                    flush_to(op);
-                    return fail(ST_GZIP_ISIZE, isize, (uint32_t)mlen);
-                }
-                mstart = op;
-                if (br.avail() < 16 || (br.peek32() & 0xffffu) != 0x8b1fu) break;  // no further member follows
-            }
-            flush_to(op);  // (once, at the very end: flushes move whole 16-byte groups, so only the last may end on an odd byte)
-            return ST_OK;
-        }
-        if (int st = zlib_header()) return st;
-        if (int st = blocks()) return st;
-        return zlib_trailer();
+        int st = GZIP ? gzip_members() : zlib_header();
+        if (!GZIP && st == ST_OK) st = blocks();
+        // Whatever the blocks came to, what they decoded goes out and into the checksum: a stream that failed delivers the
+        // bytes it had decoded by then (include/pzg.h, out_len / adler).  One flush for every way out, before the trailer
+        // compares the checksum: flushes move whole 16-byte groups, so only the last may end on an odd byte.
+        flush_to(op);
+        if (!GZIP && st == ST_OK) st = zlib_trailer();
+        return st;
     }
 
     // Deflate.hs:52-63 checkChecksum: align, fold the rest of the window, compare big-endian
-    PZG_FN int zlib_trailer()
+    PZG_FN int zlib_trailer()  // (every decoded byte has been flushed)
     {
-        flush_to(op);
         br.align_to_byte();
         if (br.avail() < 32) return fail(ST_TRUNCATED, 0, 0);
         const uint32_t t = br.peek32();
@@ -4552,6 +4553,7 @@ struct Decoder {
                     if (!res_final) return suspend_input(tpos);
                     return fail(ST_TRUNCATED, 0, 0);
                 }
+                flush_to(op);
                 const int st = zlib_trailer();
                 if (st) return st;
                 phase = PH_DONE;

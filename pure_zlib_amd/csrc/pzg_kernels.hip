@@ -112,9 +112,12 @@ __global__ __launch_bounds__(64 * CRC_WAVES) void crc32_verify_kernel(InflateArg
     __syncthreads();
     for (uint32_t i = blockIdx.x * CRC_WAVES + wave; i < a.n; i += gridDim.x * CRC_WAVES) {
         // every member's ISIZE was checked as it was decoded; a mismatch is reported unless the CRC-32 is wrong as well
-        // (zlib's order).  (Output larger than its capacity: PZG_E_OUT_TOO_SMALL, nothing stored to check.)
-        if (a.status[i] != ST_OK && a.status[i] != ST_GZIP_ISIZE) continue;
+        // (zlib's order).  A stream that failed otherwise gets the CRC-32 of the bytes it delivered, nothing is checked.
+        // (Output larger than its capacity: nothing stored to take the CRC of; adler[i] stays 0.)
+        const int32_t st = a.status[i];
+        const bool check = st == ST_OK || st == ST_GZIP_ISIZE;
         const uint64_t len = a.out_len[i];
+        if (st == ST_OUT_TOO_SMALL || len > a.out_cap[i]) continue;
         const uint8_t *p = a.out_base + a.out_off[i];
         const uint64_t pad = (CRC_BLOCK - (len & (CRC_BLOCK - 1u))) & (CRC_BLOCK - 1u);  // zero bytes in front
         const uint64_t nblk = (len + pad) / CRC_BLOCK;
@@ -146,7 +149,7 @@ __global__ __launch_bounds__(64 * CRC_WAVES) void crc32_verify_kernel(InflateArg
             reg ^= gf2_mulmod(0xffffffffu, crc_zero_bytes_factor(len, 0u));  // the initial register, advanced over the stream
             const uint32_t ours = len ? ~reg : 0u, theirs = a.gz_expect[2 * (size_t)i];
             if (a.adler) a.adler[i] = ours;
-            if (theirs != ours) {
+            if (check && theirs != ours) {
                 a.status[i] = ST_CHECKSUM;
                 if (a.detail) {
                     a.detail[2 * (size_t)i] = theirs;

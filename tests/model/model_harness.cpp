@@ -26,6 +26,31 @@ static uint32_t crc32_bits(const uint8_t *p, uint64_t n)
     return ~reg;
 }
 
+// The stream's input buffer.  By default padded on both sides with 8 bytes of 0xEE (the bit reader loads whole aligned dwords);
+// PZM_TIGHT_INPUT=1 in the environment: the allocation is exactly the aligned dwords that cover the stream, which ends at its end
+// (the stream starts `mis` = -len mod 4 bytes into it), so that under AddressSanitizer a read past those dwords is caught.
+struct InBuf {
+    uint8_t *buf;
+    const uint8_t *stream;
+};
+static InBuf in_buf(const uint8_t *in, uint64_t in_len, uint32_t front)
+{
+    InBuf b;
+    if (getenv("PZM_TIGHT_INPUT")) {
+        const uint64_t mis = (4u - (in_len & 3u)) & 3u;
+        b.buf = (uint8_t *)malloc(mis + in_len ? mis + in_len : 1);
+        memset(b.buf, 0xEE, mis);
+        if (in_len) memcpy(b.buf + mis, in, in_len);
+        b.stream = b.buf + mis;
+    } else {
+        b.buf = (uint8_t *)malloc(in_len + 16 + front);
+        memset(b.buf, 0xEE, in_len + 16 + front);
+        if (in_len) memcpy(b.buf + 8 + front, in, in_len);
+        b.stream = b.buf + 8 + front;
+    }
+    return b;
+}
+
 // the scratch a model "wave" keeps from one stream to the next (its profile is in it: strip_profile_learn)
 template <int RB, bool GZ>
 static uint32_t *&kept_scratch()
@@ -40,10 +65,7 @@ static void run_one(const uint8_t *in, uint64_t in_len, uint8_t *out, uint64_t c
     const bool gzip = GZ;
     auto *lds = (pzg::WaveLds<RB> *)aligned_alloc(16, sizeof(pzg::WaveLds<RB>));
     memset(lds, 0xA5, sizeof(*lds));  // LDS is not zero-initialised on the device either
-    // pad the input on both sides: the bit reader loads whole aligned dwords
-    uint8_t *buf = (uint8_t *)malloc(in_len + 16);
-    memset(buf, 0xEE, in_len + 16);
-    if (in_len) memcpy(buf + 8, in, in_len);
+    const InBuf ib = in_buf(in, in_len, 0);
     pzg::Decoder<RB, GZ> dec(*lds);
     pzg::StreamResult sr;
     // the wave's token scratch (strips); PZM_NO_STRIPS=1 in the environment: the windows alone, as on a launch without scratch
@@ -61,7 +83,7 @@ static void run_one(const uint8_t *in, uint64_t in_len, uint8_t *out, uint64_t c
             strip = kept;
     }
     dec.strip = strip;
-    dec.run(buf + 8, in_len, out, cap, &sr);
+    dec.run(ib.stream, in_len, out, cap, &sr);
     if (fresh) free(strip);
     r->status = sr.status;
     r->detail0 = sr.detail0;
@@ -69,11 +91,12 @@ static void run_one(const uint8_t *in, uint64_t in_len, uint8_t *out, uint64_t c
     r->adler = sr.adler;
     r->out_len = sr.out_len;
     r->in_used = sr.in_used;
-    if (gzip && (sr.status == pzg::ST_OK || sr.status == pzg::ST_GZIP_ISIZE)) {  // the verify pass of the gzip launch
-        const uint32_t ours = crc32_bits(out, sr.out_len < cap ? sr.out_len : cap);
+    if (gzip) {  // the verify pass of the gzip launch: the CRC-32 of what was delivered, 0 when the output outgrew its capacity
+        const bool check = sr.status == pzg::ST_OK || sr.status == pzg::ST_GZIP_ISIZE;
+        const uint32_t ours = sr.out_len > cap ? 0u : crc32_bits(out, sr.out_len);
         r->adler = ours;
-        if (sr.out_len > cap) {
-            // (not stored: nothing to check; a length mismatch stays what it is)
+        if (sr.out_len > cap || !check) {
+            // (not stored: nothing to check; a length mismatch stays what it is.  A stream that failed otherwise: no check)
         } else if (sr.gz_crc != ours) {
             r->status = pzg::ST_CHECKSUM;
             r->detail0 = sr.gz_crc;
@@ -82,7 +105,7 @@ static void run_one(const uint8_t *in, uint64_t in_len, uint8_t *out, uint64_t c
             r->detail0 = r->detail1 = 0;
         }
     }
-    free(buf);
+    free(ib.buf);
     free(lds);
 }
 
@@ -201,13 +224,14 @@ int pzm_bundle(const uint8_t *const *ins, const uint64_t *in_lens, uint8_t *cons
     for (uint32_t k = 0; k < 64u; ++k) {
         const bool have = k < n;
         const uint64_t len = have ? in_lens[k] : 0, cap = have ? caps[k] : 0;
+        const uint8_t *stream = nullptr;
         if (have) {
-            bufs[k] = (uint8_t *)malloc(len + 16 + (k & 3u));
-            memset(bufs[k], 0xEE, len + 16 + (k & 3u));
-            if (len) memcpy(bufs[k] + 8 + (k & 3u), ins[k], len);  // (every alignment of a stream's first byte)
+            const InBuf ib = in_buf(ins[k], len, k & 3u);  // (padded: every alignment of a stream's first byte)
+            bufs[k] = ib.buf;
+            stream = ib.stream;
         }
         const bool on = have && len >= 8u && len < B::MAX_BYTES && cap < B::MAX_BYTES;
-        bi.IN.v[k] = have ? bufs[k] + 8 + (k & 3u) : (const uint8_t *)common;
+        bi.IN.v[k] = have ? stream : (const uint8_t *)common;
         bi.OUT.v[k] = have ? outs[k] : nowhere;
         bi.LEN.v[k] = on ? (uint32_t)len : 0u;
         bi.CAP.v[k] = on ? (uint32_t)cap : 0u;

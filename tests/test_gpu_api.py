@@ -452,12 +452,14 @@ def test_host_pinned_arenas(gpu_ctx, oracle):
                 for x, y in zip(ref, got):
                     assert np.array_equal(x, y)
                 assert got[1][7] == 1 and got[1][n - 5] == 14 and int((got[1] == 0).sum()) == n - 2
-                for k in range(n):  # (a failed stream's bytes are unspecified: only what it produced before the error was flushed)
-                    if got[1][k] not in (0, 14):
-                        continue
+                for k in range(n):  # (a failed stream delivers what it had decoded by then: include/pzg.h)
                     nb = int(min(got[0][k], out_cap[k]))
                     lo = int(out_off[k])
                     assert np.array_equal(a_out.a[lo:lo + nb], ref_out[lo:lo + nb]), k
+                r, o = oracle.decompress(streams[7], int(out_cap[7]))
+                lo = int(out_off[7])
+                assert r.status == 1 and int(got[0][7]) == r.out_len and a_out.a[lo:lo + len(o)].tobytes() == o
+                assert int(got[4][7]) == zlib.adler32(o) and int(ref[4][7]) == zlib.adler32(o)
                 assert (a_out.a[:guard] == 0xCD).all() and (a_out.a[int(out_off[-1] + out_cap[-1]):] == 0xCD).all()
             finally:
                 if group is not None:

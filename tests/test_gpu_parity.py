@@ -42,7 +42,21 @@ def run_batch(ctx, streams, caps, align=16, gzip=False):
     out_cap = np.array(caps, dtype=np.uint64)
     res = ctx.decompress_many_raw(in_buf, in_off, in_len, out_buf, out_off, out_cap, gzip=gzip)
     outs = [out_buf[int(out_off[k]):int(out_off[k]) + min(int(res[0][k]), caps[k])].tobytes() for k in range(n)]
+    # the staged path writes min(out_len, cap) bytes per extent and nothing else (include/pzg.h): the rest keeps its fill
+    written = np.zeros(out_buf.size, dtype=bool)
+    for k in range(n):
+        written[int(out_off[k]):int(out_off[k]) + len(outs[k])] = True
+    assert (out_buf[~written] == 0xCD).all(), "bytes outside the streams' min(out_len, cap) were written"
     return res, outs, out_buf, out_off
+
+
+def check_failed(k, r, o, cap, out_len, outs, adler, gzip=False):
+    """include/pzg.h: a stream that failed (status neither 0 nor 14) delivers what the oracle (r, o) had decoded by then --
+    out_len, the bytes below the capacity -- and adler[] is their Adler-32 (gzip: CRC-32), 0 when out_len exceeds the capacity."""
+    assert int(out_len[k]) == r.out_len, (k, r.status, int(out_len[k]), r.out_len)
+    assert outs[k] == o, (k, r.status, r.out_len, cap)
+    want = 0 if r.out_len > cap else (zlib.crc32(o) if gzip else zlib.adler32(o))
+    assert int(adler[k]) == want, (k, r.status, hex(int(adler[k])), hex(want))
 
 
 @pytest.mark.parametrize("name", REF_CASES)
@@ -115,6 +129,7 @@ def test_corrupt_streams_vs_oracle(ctx, oracle):
             # same constructor class AND same message as the reference (restated by the oracle)
             err = Z.error_from_status(streams[k], int(status[k]), detail[k])
             assert err.show() == r.message.decode(), (k, err.show(), r.message.decode())
+            check_failed(k, r, o, caps[k], out_len, outs, adler)
 
 
 def test_strips_valid_and_corrupt_vs_oracle(ctx, oracle):
@@ -145,6 +160,35 @@ def test_strips_valid_and_corrupt_vs_oracle(ctx, oracle):
         else:
             err = Z.error_from_status(streams[k], int(status[k]), detail[k])
             assert err.show() == r.message.decode(), (k, err.show(), r.message.decode())
+            check_failed(k, r, o, caps[k], out_len, outs, adler)
+
+
+def test_staged_path_failed_streams_get_their_own_bytes(ctx, oracle):
+    """The staged host path copies min(out_len, cap) bytes of every extent out of the context's staging arena, failed streams'
+    too.  Batch A (valid streams) and then batch B (truncated and corrupted streams of OTHER data, the same sizes: the same places
+    in the staging arena): B's extents hold the oracle's prefixes and never what A left in the arena."""
+    n, size = 96, 6000
+    a_data = [corpus.zipf_text(size, 100 + k) for k in range(n)]
+    b_data = [corpus.mixed_data(size, 300 + k) for k in range(n)]
+    a_streams = [zlib.compress(d, 6) for d in a_data]
+    b_streams = []
+    for k, d in enumerate(b_data):
+        z = zlib.compress(d, [1, 6, 0][k % 3])
+        b_streams.append(z[: len(z) * (20 + k % 70) // 100] if k % 2 == 0 else corpus.corrupt(z, 900 + k))
+    caps = [size] * n
+    (out_len, status, _, _, adler), outs, _, _ = run_batch(ctx, a_streams, caps)
+    assert (status == 0).all() and outs == a_data
+    (out_len, status, detail, _, adler), outs, _, _ = run_batch(ctx, b_streams, caps)
+    failed = differ = 0
+    for k in range(n):
+        r, o = oracle.decompress(b_streams[k], caps[k])
+        assert int(status[k]) == r.status, (k, int(status[k]), r.status)
+        if r.status in (0, 14):
+            continue
+        failed += 1
+        check_failed(k, r, o, caps[k], out_len, outs, adler)
+        differ += outs[k] != a_data[k][: len(outs[k])]
+    assert failed >= n // 2 and differ >= n // 3, (failed, differ)
 
 
 def _check_against_oracle(oracle, streams, caps, res, outs, datas=None):
@@ -161,6 +205,7 @@ def _check_against_oracle(oracle, streams, caps, res, outs, datas=None):
         else:
             err = Z.error_from_status(streams[k], int(status[k]), detail[k])
             assert err.show() == r.message.decode(), (k, err.show(), r.message.decode())
+            check_failed(k, r, o, caps[k], out_len, outs, adler)
 
 
 def test_exotic_streams_vs_oracle(ctx, oracle):
@@ -613,6 +658,8 @@ def test_gzip_members_extension(ctx, oracle):
             assert outs[k] == o and int(crc[k]) == r.adler
         elif r.status in (10, 19):
             assert [int(detail[k][0]), int(detail[k][1])] == [r.detail0, r.detail1]
+        if r.status not in (0, 14):
+            check_failed(k, r, o, caps[k], out_len, outs, crc, gzip=True)
     # the mirror API
     rs = P.gzip_decompress_many(streams[:20], ctx=ctx)
     assert rs == [P.Right(d) for d in datas[:20]]

@@ -34,9 +34,11 @@ def _build_model(flags):
     M.pzm_decompress_gzip.argtypes = M.pzm_decompress.argtypes
 
     def run(z, cap, rb, gzip=False):
-        out = C.create_string_buffer(max(cap, 1))
+        # GUARD sentinel bytes follow the capacity: nothing may be written past it, whatever the stream does
+        out = C.create_string_buffer(b"\xa5" * cap + GUARD, cap + len(GUARD))
         r = R()
         assert (M.pzm_decompress_gzip if gzip else M.pzm_decompress)(z, len(z), out, cap, rb, C.byref(r)) == 0
+        assert out.raw[cap:] == GUARD, ("written past the capacity", cap, r.status, r.out_len)
         return r, out.raw[: min(r.out_len, cap)]
     return run
 
@@ -54,13 +56,31 @@ def model_bad_guesses():
     return _build_model(["-DPZG_STRIP_BACK=8", "-DPZG_STRIP_ROUNDS=1"])
 
 
-def same(ro, oo, rm, om):
+GUARD = bytes(range(0x40, 0x80))  # 64 bytes that must stay as they are past a stream's capacity
+
+
+def failed_adler(ro, cap):
+    """What include/pzg.h promises in adler[] for a stream that failed (status neither 0 nor 14): the checksum of the bytes it
+    decoded -- the oracle's -- or 0 when they outgrew the capacity."""
+    return 0 if ro.out_len > cap else ro.adler
+
+
+def same(ro, oo, rm, om, cap=None):
+    """The model's (rm, om) is the oracle's (ro, oo).  A failed stream (status neither 0 nor 14) delivers what the oracle had
+    decoded by then: out_len, the bytes below the capacity (om / oo hold min(out_len, cap) of them) and their checksum (0 when
+    out_len exceeds the capacity; `cap` defaults to len(om) when that cannot be told from the bytes)."""
     if ro.status != rm.status:
         return False
     if ro.status == 0:
         return oo == om and ro.adler == rm.adler and ro.in_used == rm.in_used and ro.out_len == rm.out_len
     if ro.status == 14:
         return ro.out_len == rm.out_len
+    if ro.out_len != rm.out_len or oo != om:
+        return False
+    if cap is None and ro.out_len > len(oo):
+        cap = len(oo)
+    if rm.adler != (ro.adler if cap is None else failed_adler(ro, cap)):
+        return False
     if ro.status in (3, 4, 6, 10, 11, 12, 13):
         return (ro.detail0, ro.detail1) == (rm.detail0, rm.detail1)
     if ro.status == 7:

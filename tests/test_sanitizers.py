@@ -36,6 +36,35 @@ def test_oracle_and_kernel_model_under_asan_ubsan(exe, rb, cap):
     assert "0 mismatches" in r.stdout
 
 
+@pytest.mark.parametrize("rb", [11, 15])
+def test_reads_stay_inside_the_dwords_that_cover_the_stream(exe, rb):
+    """ADVICE r6 (bundle_core.h: the bundles' reader): with PZM_TIGHT_INPUT every stream ends at the end of an allocation the size of
+    the aligned dwords that cover it, so ASan catches a read past them -- by the ordinary decoder and by the bundles' lanes.  Streams
+    of the fixed code of every length modulo 4 (what the bundles take), truncated ones, and the pinned vectors."""
+    import zlib
+    import corpus
+    out, d = exe
+    files = []
+    for k in range(160):
+        t = corpus.zipf_text(1 + (k * 37) % 3000, 700 + k)
+        co = zlib.compressobj(1, zlib.DEFLATED, 15, 8, zlib.Z_FIXED)
+        z = co.compress(t) + co.flush()
+        z = z if k % 3 else z[: max(1, len(z) - 1 - k % 11)]
+        p = d / ("tight%d.z" % k)
+        p.write_bytes(z)
+        files.append(str(p))
+    for v in load_vectors():
+        p = d / (v["name"] + ".z")
+        if not p.exists():
+            p.write_bytes(bytes.fromhex(v["z"]))
+        files.append(str(p))
+    r = subprocess.run([out, str(1 << 14), str(rb)] + files, capture_output=True, text=True, timeout=900,
+                       env=dict(os.environ, PZM_TIGHT_INPUT="1", PZM_SAN_BUNDLES="1", ASAN_OPTIONS="detect_leaks=1",
+                                UBSAN_OPTIONS="print_stacktrace=1"))
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert "0 mismatches" in r.stdout
+
+
 @pytest.mark.parametrize("san", ["thread", "address,undefined"])
 def test_helper_thread_pool_under_sanitizers(tmp_path, san):
     """The persistent helper pool of the host-pointer paths (pure_zlib_amd/csrc/pzg_helpers.h; round 4): four threads call run()
