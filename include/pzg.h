@@ -127,6 +127,25 @@ extern "C" {
                               * path, without this flag, writes out_len[i] bytes per extent and nothing else); gaps of the input arena travel over the link, so pack tightly
                               * (16-byte aligned extents keep the wide store path).  Pageable memory under this flag is still
                               * correct, only slower.  Not combined with preset dictionaries. */
+#define PZG_RAW         32u  /* (0.5) EXTENSION: every stream is a bare RFC 1951 stream -- what a deflated member of a .zip / .jar / .whl
+                              * holds, system zlib's wbits = -15: no header, no trailer, no checksum check.  Everything else means what
+                              * it means for zlib streams:
+                              *   in_used[i]  the input bytes up to and including the byte that holds the last bit of the final block;
+                              *               what follows is left alone
+                              *   adler[i]    the Adler-32 of the decoded bytes, reported and not checked (failed and over-capacity
+                              *               streams: the rules of pzg_decompress_many below)
+                              *   status[i]   PZG_E_HDR_*, PZG_E_CHECKSUM and PZG_E_DICT cannot occur; input that runs out before the
+                              *               final block ends (in_len[i] = 0 too) is PZG_E_TRUNCATED; the bit offset in detail[1] of
+                              *               PZG_E_HUFF_BUILD counts from the first bit of the raw stream, so that pzg_error_message
+                              *               over the raw bytes gives the text
+                              * With pzg_decompress_many_dict a stream with dict_len[i] > 0 decodes with that dictionary as the history
+                              * in front of its output, unconditionally -- there is no FDICT bit and no DICTID (zlib's raw
+                              * inflateSetDictionary); dict_len[i] = 0: plain raw.  Not combined with PZG_GZIP (PZG_RC_BAD_ARG).
+                              * Raw launches do not use the bundles (PZG_OPT_BUNDLES), and the pzg_decoder_* objects stay zlib-only. */
+#define PZG_CRC32       64u  /* (0.5) only together with PZG_RAW (PZG_RC_BAD_ARG otherwise): adler[i] holds the CRC-32 (RFC 1952 section 8)
+                              * of the bytes delivered instead of their Adler-32 -- computed on the device in one more pass over the
+                              * output, 0 when out_len[i] > out_cap[i].  Nothing is verified: the caller owns the expected value (a ZIP
+                              * central directory, say). */
 
 typedef struct pzg_ctx pzg_ctx;
 
@@ -217,6 +236,7 @@ PZG_API void  pzg_host_free(void *p);
  *   detail[2n]             two detail words per stream (see the status table); may be NULL
  *   in_used[n]             input bytes consumed incl. the Adler trailer; may be NULL
  *   adler[n]               Adler-32 computed over the decoded bytes; may be NULL.  With PZG_GZIP: the CRC-32 of them.
+ * (PZG_RAW: bare RFC 1951 streams instead, see the flag; with PZG_CRC32 adler[] holds their CRC-32.)
  *
  * A stream that FAILED (status neither PZG_OK nor PZG_E_OUT_TOO_SMALL) delivers what the reference had emitted before the error:
  *   out_len[i]   those bytes -- nothing of a stored block whose bytes run out (Deflate.hs:77: nextBlock reads the block whole
@@ -250,7 +270,7 @@ PZG_API int pzg_decompress_many(pzg_ctx *ctx,
  * enqueued on its own device's stream -- nothing crosses PCIe or xGMI, no collective: the streams are independent -- and
  * the call returns when all of them have finished (with PZG_ASYNC: at once; pzg_sync() waits for every device).
  * Several batches may name the same shard (they run one after the other on its stream).  flags: PZG_ASYNC, PZG_GZIP,
- * PZG_LPT_ORDER (PZG_DEVICE_PTRS is implied).
+ * PZG_LPT_ORDER, PZG_RAW, PZG_CRC32 (PZG_DEVICE_PTRS is implied).
  */
 typedef struct pzg_device_batch {
     uint32_t shard;  /* which device of the context the pointers below live on */
@@ -270,6 +290,7 @@ PZG_API int pzg_decompress_many_sharded(pzg_ctx *ctx, const pzg_device_batch *ba
  * dictionary extent per stream (dict_len[i] = 0: none): a stream whose header has FDICT set and that has a
  * dictionary checks DICTID against the dictionary's Adler-32 (PZG_E_DICT) and decodes with the dictionary as the
  * history in front of its output; every other stream behaves as in pzg_decompress_many.  dict_* may be NULL.
+ * With PZG_RAW (0.5) the dictionary of a stream that has one is its history unconditionally: see the flag.
  */
 PZG_API int pzg_decompress_many_dict(pzg_ctx *ctx,
                              const uint8_t *in_base, const uint64_t *in_off, const uint64_t *in_len,

@@ -7,6 +7,7 @@ Only what the hot path needs lives here:
   shard.py   host-side sharding of a batch of streams over the GPUs of a node
   incremental.py, deflate_cli.py, benchmark.py   the reference's streaming protocol, CLI and criterion harness
              over the same path; gzip members (row 4) are `gzip_decompress_many`
+  zip.py     ZIP archives read and tested in one launch (raw DEFLATE members, sizes and CRC-32s from the central directory)
   cxx/       the same module mirror in C++ (header-only)
 
 There is no CPU fallback: importing works anywhere, computing needs libpzg.so and a gfx950 device.
@@ -15,5 +16,5 @@ from . import _ffi  # noqa: F401
 from .zlib import (  # noqa: F401
     ChecksumError, Context, DecompressionError, DecompressionError_, FormatError, HeaderError,
     HuffmanTreeError, Left, Right, adler32, decompress, decompress_many, decompressMany, default_context,
-    gzip_decompress_many,
+    gzip_decompress_many, raw_decompress, raw_decompress_many,
 )

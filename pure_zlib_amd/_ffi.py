@@ -38,6 +38,8 @@ ASYNC = 2
 GZIP = 4  # extension: streams are RFC 1952 members; adler[] holds the CRC-32
 LPT_ORDER = 8  # device-pointer batches: launch the longest streams first
 HOST_PINNED = 16  # host-pointer batches in page-locked arenas (pzg_host_alloc), extents ascending: no staging, no copy-out
+RAW = 32  # extension: streams are bare RFC 1951 (no header, no trailer, nothing checked); adler[] holds the Adler-32, reported only
+CRC32 = 64  # with RAW only: adler[] holds the CRC-32 of the bytes delivered (computed on the device, checked against nothing)
 OPT_RING_BITS = 1
 OPT_HOST_THREADS = 2
 OPT_SCRATCH_BYTES = 3

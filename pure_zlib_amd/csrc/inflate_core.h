@@ -485,8 +485,11 @@ struct BitReader {
 // ---- decoder state (all wave-uniform) -----------------------------------------------------------
 // GZIP: the streams are RFC 1952 members (an extension; its own kernel instances, so the zlib ones carry none of it)
 // RES: the resumable instance (decompressIncremental): suspends when the input or the output room runs out
-template <int RING_BITS, bool GZIP = false, bool RES = false>
+// RAW: the streams are bare RFC 1951 (an extension: what a ZIP member holds): no header, no trailer, nothing checked; its own kernel
+// instances again (pzg_inflate_kernel.h inflate_raw_kernel)
+template <int RING_BITS, bool GZIP = false, bool RES = false, bool RAW = false>
 struct Decoder {
+    static_assert(!RAW || (!GZIP && !RES), "a raw stream has no container and no resumable instance");
     static constexpr uint32_t RING = 1u << RING_BITS;
     static constexpr uint32_t RMASK = RING - 1u;
     static constexpr uint32_t FLUSH_AT = RING - 1024u;
@@ -4328,14 +4331,27 @@ struct Decoder {
 
     PZG_FN int decode()
     {
-        int st = GZIP ? gzip_members() : zlib_header();
+        int st;
+        // (raw: the blocks start at bit 0 and the stream ends with the final block -- run() rounds in_used up to the byte that holds
+        // its last bit)
+        if constexpr (RAW) st = raw_dictionary();
+        else st = GZIP ? gzip_members() : zlib_header();
         if (!GZIP && st == ST_OK) st = blocks();
         // Whatever the blocks came to, what they decoded goes out and into the checksum: a stream that failed delivers the
         // bytes it had decoded by then (include/pzg.h, out_len / adler).  One flush for every way out, before the trailer
         // compares the checksum: flushes move whole 16-byte groups, so only the last may end on an odd byte.
         flush_to(op);
-        if (!GZIP && st == ST_OK) st = zlib_trailer();
+        if (!GZIP && !RAW && st == ST_OK) st = zlib_trailer();
         return st;
+    }
+
+    // A raw stream's dictionary (zlib's raw inflateSetDictionary): there is no FDICT bit and no DICTID, it is the history as it stands
+    PZG_FN int raw_dictionary()
+    {
+        if (dict_len == 0u) return ST_OK;
+        if (RING_BITS != 15) return fail(ST_RETRY_FULL_RING, 0, 0);  // decoded by the 32 KiB-ring instance only
+        install_dictionary();
+        return ST_OK;
     }
 
     // Deflate.hs:52-63 checkChecksum: align, fold the rest of the window, compare big-endian

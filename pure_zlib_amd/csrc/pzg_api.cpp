@@ -400,6 +400,14 @@ void ctx_unref(pzg_ctx *ctx)
 
 inline bool ctx_live(const pzg_ctx *ctx) { return ctx && !ctx->closed.load(std::memory_order_acquire); }
 
+// InflateArgs::raw of a call's flags; and whether the container flags go together (PZG_RAW excludes PZG_GZIP, PZG_CRC32 needs PZG_RAW)
+inline uint32_t raw_mode(uint32_t flags) { return !(flags & PZG_RAW) ? 0u : (flags & PZG_CRC32) ? 2u : 1u; }
+inline bool container_flags_ok(uint32_t flags)
+{
+    if ((flags & PZG_RAW) && (flags & PZG_GZIP)) return false;
+    return (flags & PZG_RAW) || !(flags & PZG_CRC32);
+}
+
 // ---- the device-pointer path: everything already lives on shard 0's device -------------------------------------
 int launch_device(pzg_ctx *ctx, Shard &sh, pzg::InflateArgs a, uint32_t flags)
 {
@@ -415,6 +423,7 @@ int launch_device(pzg_ctx *ctx, Shard &sh, pzg::InflateArgs a, uint32_t flags)
         a.gzip = 1;
         a.gz_expect = (uint32_t *)sh.a_gz[slot].p;
     }
+    a.raw = raw_mode(flags);
     if (flags & PZG_LPT_ORDER) {  // longest streams first: a launch permutation built on the device from out_cap[]
         int rc = arena_reserve(ctx, sh.a_order[slot], 4 * (size_t)a.n + 1024);
         if (rc != PZG_RC_OK) return rc;
@@ -438,7 +447,7 @@ int launch_device(pzg_ctx *ctx, Shard &sh, pzg::InflateArgs a, uint32_t flags)
         HIP_TRY(ctx, pzg::launch_profile_switch(a.strip, (uint32_t)(sh.a_strip[ss].cap / pzg::inflate_strip_wave_bytes()), off, sh.stream));
         sh.a_strip[ss].prof_off = off;
     }
-    a.bundle = (ctx->bundles.load() == 2 || (ctx->bundles.load() == 1 && a.n >= BUNDLE_MIN_STREAMS)) && !(flags & PZG_GZIP) && !a.dict_len ? 1u : 0u;
+    a.bundle = (ctx->bundles.load() == 2 || (ctx->bundles.load() == 1 && a.n >= BUNDLE_MIN_STREAMS)) && !(flags & (PZG_GZIP | PZG_RAW)) && !a.dict_len ? 1u : 0u;
     if (a.bundle && ctx->bundles.load() == 1 && sh.h_bundle) {
         // (the probe costs a launch of dynamic-code streams ~1 %: the bundle kernel, and two words every stream-wave reads first)
         if (sh.bundle_pending && hipEventQuery(sh.ev_bundle) == hipSuccess) {
@@ -811,6 +820,7 @@ int host_path(pzg_ctx *ctx, Shard &sh, const HostBatch &b, const uint32_t *idx, 
             a.gzip = 1;
             a.gz_expect = (uint32_t *)ln.d_gz[s].p;
         }
+        a.raw = raw_mode(b.flags);
 #if defined(PZG_PROFILE)
         a.prof_out = ctx->prof_buf ? (uint64_t *)ctx->prof_buf + 16 * (size_t)r.lo : nullptr;
 #endif
@@ -924,6 +934,7 @@ int dict_path(pzg_ctx *ctx, Shard &sh, const HostBatch &b, const uint8_t *dict_b
     a.detail = a.adler + n;
     a.n = n;
     a.counter = ln.d_counter;
+    a.raw = raw_mode(b.flags);  // (raw streams: the dictionary is the history, whatever the stream says)
     strip_for_launch(ctx, ln.d_strip, sh.num_cus, n, 0u, a);
     HIP_TRY(ctx, pzg::launch_inflate(a, ctx->ring_bits, sh.num_cus, st));
     std::vector<uint8_t> res(32 * (size_t)n), hout(op + 16);
@@ -1143,7 +1154,8 @@ int pzg_decompress_many_dict(pzg_ctx *ctx, const uint8_t *in_base, const uint64_
 {
     if (!ctx_live(ctx)) return PZG_RC_BAD_ARG;
     const bool with_dict = dict_base && dict_off && dict_len;
-    if (with_dict && (flags & PZG_GZIP)) return PZG_RC_BAD_ARG;  // (preset dictionaries are a zlib-container notion)
+    if (with_dict && (flags & PZG_GZIP)) return PZG_RC_BAD_ARG;  // (preset dictionaries are a zlib-container notion; raw streams take them too)
+    if (!container_flags_ok(flags)) return PZG_RC_BAD_ARG;
     if (n == 0) return PZG_RC_OK;
     if (!in_base || !in_off || !in_len || !out_off || !out_cap || !out_len || !status) return PZG_RC_BAD_ARG;
     if ((flags & PZG_ASYNC) && !(flags & PZG_DEVICE_PTRS)) return PZG_RC_BAD_ARG;
@@ -1261,7 +1273,8 @@ int pzg_decompress_many_dict(pzg_ctx *ctx, const uint8_t *in_base, const uint64_
 int pzg_decompress_many_sharded(pzg_ctx *ctx, const pzg_device_batch *batches, uint32_t nbatches, uint32_t flags)
 {
     if (!ctx_live(ctx) || (!batches && nbatches)) return PZG_RC_BAD_ARG;
-    if (flags & ~(PZG_ASYNC | PZG_GZIP | PZG_LPT_ORDER | PZG_DEVICE_PTRS)) return PZG_RC_BAD_ARG;
+    if (flags & ~(PZG_ASYNC | PZG_GZIP | PZG_LPT_ORDER | PZG_DEVICE_PTRS | PZG_RAW | PZG_CRC32)) return PZG_RC_BAD_ARG;
+    if (!container_flags_ok(flags)) return PZG_RC_BAD_ARG;
     for (uint32_t b = 0; b < nbatches; ++b) {
         const pzg_device_batch &q = batches[b];
         if (q.shard >= ctx->shards.size()) return PZG_RC_BAD_ARG;
@@ -1287,7 +1300,7 @@ int pzg_decompress_many_sharded(pzg_ctx *ctx, const pzg_device_batch *batches, u
             a.in_used = q.in_used;
             a.adler = q.adler;
             a.n = q.n;
-            rc = launch_device(ctx, *ctx->shards[q.shard], a, (flags & (PZG_GZIP | PZG_LPT_ORDER)) | PZG_DEVICE_PTRS | PZG_ASYNC);
+            rc = launch_device(ctx, *ctx->shards[q.shard], a, (flags & (PZG_GZIP | PZG_LPT_ORDER | PZG_RAW | PZG_CRC32)) | PZG_DEVICE_PTRS | PZG_ASYNC);
         }
         // ... then waited for, unless the caller does that (on an error too: nothing enqueued may outlive a failed call)
         if (!(flags & PZG_ASYNC) || rc != PZG_RC_OK) {

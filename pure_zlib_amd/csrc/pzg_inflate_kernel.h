@@ -1,5 +1,5 @@
 // pzg_inflate_kernel.h -- inflate_kernel<RING_BITS, FIXUP, GZIP>, the persistent stream-wave kernel around Decoder::run()
-// (inflate_core.h), for the two translation units that instantiate it: pzg_kernels.hip (the zlib instances) and
+// (inflate_core.h), and inflate_raw_kernel<RING_BITS, FIXUP>, the same around the raw decoder, for the two translation units that instantiate it: pzg_kernels.hip (the zlib instances) and
 // pzg_kernels_b.hip (the gzip instances and the resumable decoder's kernel, compiled without the SDWA peephole -- see the Makefile).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -163,5 +163,60 @@ __global__ __launch_bounds__(64, waves_per_simd(RING_BITS, GZIP)) void inflate_k
     }
 }
 
+// The raw instances (PZG_RAW: bare RFC 1951 streams, an extension): the same persistent stream-waves, work counter, launch order,
+// scratch slices and hand-back to the 32 KiB-ring pass around Decoder<RING_BITS, false, false, true>.  A kernel of its own name,
+// so that the zlib and gzip instances above are compiled from exactly what they were compiled from before; no bundles (the
+// launcher clears InflateArgs::bundle), and with a dictionary every stream that has one decodes with it as its history.
+template <int RING_BITS, bool FIXUP>
+__global__ __launch_bounds__(64, waves_per_simd(RING_BITS)) void inflate_raw_kernel(InflateArgs)
+{
+    typedef Decoder<RING_BITS, false, false, true> RawDecoder;
+    __shared__ WaveLds<RING_BITS> lds;
+    if (FIXUP && __builtin_nontemporal_load(launch_args()->counter + 1) == 0u) return;  // nothing was handed back
+    if (threadIdx.x == 0) lds.fixed_ready = 0u;  // LDS is not zeroed at launch
+    __syncthreads();
+    for (;;) {
+        uint32_t i = 0;
+        StreamResult r;
+        {
+            LaunchArgs a = launch_args();
+            if (threadIdx.x == 0) i = atomicAdd(a->counter, 1u);
+            i = uni(i);
+            if (i >= a->n) break;
+            if (a->order) i = a->order[i];
+            if (FIXUP && a->status[i] != ST_RETRY_FULL_RING) continue;
+            RawDecoder dec(lds);
+            if (FIXUP) {
+                // (the fixup pass decodes without scratch.  The null is made opaque: with a pointer it KNOWS to be null the compiler
+                // specialises the decoder into something its own backend then refuses -- "illegal VGPR to SGPR copy", ROCm 7.2)
+                uint32_t *none = nullptr;
+                asm volatile("" : "+s"(none));
+                dec.strip = none;
+            }
+            if (!FIXUP && a->strip && blockIdx.x < a->strip_waves) dec.strip = a->strip + (size_t)blockIdx.x * RawDecoder::STRIP_WORDS;
+            const uint8_t *dict = nullptr;
+            uint32_t dict_len = 0;
+            if (a->dict_len) {
+                const uint64_t dl = a->dict_len[i];
+                dict = a->dict_base + a->dict_off[i];
+                dict_len = uni(dl > 0xffffffffull ? 0xffffffffu : (uint32_t)dl);
+            }
+            dec.run(a->in_base + a->in_off[i], a->in_len[i], a->out_base + a->out_off[i], a->out_cap[i], &r, dict, dict_len);
+        }
+        LaunchArgs a = launch_args();
+        if (threadIdx.x == 0) {
+            a->status[i] = r.status;
+            if (!FIXUP && r.status == ST_RETRY_FULL_RING) atomicAdd(a->counter + 1, 1u);
+            a->out_len[i] = r.out_len;
+            if (a->detail) {
+                a->detail[2 * (size_t)i] = r.detail0;
+                a->detail[2 * (size_t)i + 1] = r.detail1;
+            }
+            if (a->in_used) a->in_used[i] = r.in_used;
+            if (a->adler) a->adler[i] = r.adler;  // (PZG_CRC32: crc32_report_kernel then writes the CRC-32 over it)
+        }
+        __syncthreads();
+    }
+}
 
 }  // namespace pzg

@@ -79,8 +79,12 @@ __device__ __forceinline__ uint32_t crc_zero_bytes_factor(uint64_t n, uint32_t s
 // tables ADV) and then over its own 16 (slicing-by-4, sixteen lookups in T); at the end the accumulators are moved
 // over the 16 (63 - l) bytes behind each lane's last chunk and XORed together, and the contribution of the real
 // initial register 0xffffffff -- advanced over the whole length -- is added.
+// VERIFY: the gzip form -- the CRC-32 is compared with the one the member trailers ask for (gz_expect) and a mismatch rewrites the
+// stream's status.  Without it (PZG_RAW | PZG_CRC32): report only -- adler[i] gets the CRC-32 of the bytes delivered, 0 for a stream
+// that outgrew its capacity; nothing is compared, nothing else is written and no gz_expect arena exists.
 constexpr uint32_t CRC_BLOCK = 1024u, CRC_WAVES = 4u;
-__global__ __launch_bounds__(64 * CRC_WAVES) void crc32_verify_kernel(InflateArgs a)
+template <bool VERIFY>
+__device__ __forceinline__ void crc32_pass(const InflateArgs &a)
 {
     __shared__ uint32_t T[4][256], ADV[4][256];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
@@ -117,7 +121,10 @@ __global__ __launch_bounds__(64 * CRC_WAVES) void crc32_verify_kernel(InflateArg
         const int32_t st = a.status[i];
         const bool check = st == ST_OK || st == ST_GZIP_ISIZE;
         const uint64_t len = a.out_len[i];
-        if (st == ST_OUT_TOO_SMALL || len > a.out_cap[i]) continue;
+        if (st == ST_OUT_TOO_SMALL || len > a.out_cap[i]) {
+            if (!VERIFY && lane == 0u && a.adler) a.adler[i] = 0u;  // (the raw kernels left the Adler-32 there)
+            continue;
+        }
         const uint8_t *p = a.out_base + a.out_off[i];
         const uint64_t pad = (CRC_BLOCK - (len & (CRC_BLOCK - 1u))) & (CRC_BLOCK - 1u);  // zero bytes in front
         const uint64_t nblk = (len + pad) / CRC_BLOCK;
@@ -147,18 +154,23 @@ __global__ __launch_bounds__(64 * CRC_WAVES) void crc32_verify_kernel(InflateArg
         for (int o = 32; o > 0; o >>= 1) reg ^= (uint32_t)__shfl_xor((int)reg, o, 64);
         if (lane == 0u) {
             reg ^= gf2_mulmod(0xffffffffu, crc_zero_bytes_factor(len, 0u));  // the initial register, advanced over the stream
-            const uint32_t ours = len ? ~reg : 0u, theirs = a.gz_expect[2 * (size_t)i];
+            const uint32_t ours = len ? ~reg : 0u;
             if (a.adler) a.adler[i] = ours;
-            if (check && theirs != ours) {
-                a.status[i] = ST_CHECKSUM;
-                if (a.detail) {
-                    a.detail[2 * (size_t)i] = theirs;
-                    a.detail[2 * (size_t)i + 1] = ours;
+            if (VERIFY) {
+                const uint32_t theirs = a.gz_expect[2 * (size_t)i];
+                if (check && theirs != ours) {
+                    a.status[i] = ST_CHECKSUM;
+                    if (a.detail) {
+                        a.detail[2 * (size_t)i] = theirs;
+                        a.detail[2 * (size_t)i + 1] = ours;
+                    }
                 }
             }
         }
     }
 }
+__global__ __launch_bounds__(64 * CRC_WAVES) void crc32_verify_kernel(InflateArgs a) { crc32_pass<true>(a); }
+__global__ __launch_bounds__(64 * CRC_WAVES) void crc32_report_kernel(InflateArgs a) { crc32_pass<false>(a); }
 
 // stream-waves of a launch: the residency of the chip, or one per stream if there are fewer
 static uint32_t launch_waves(int ring_bits, int num_cus, uint32_t n, uint32_t gzip)
@@ -206,7 +218,7 @@ hipError_t launch_inflate(const InflateArgs &a_in, int ring_bits, int num_cus, h
 {
     if (a_in.n == 0) return hipSuccess;
     InflateArgs a = a_in;
-    if (a.gzip || a.dict_len) a.bundle = 0u;
+    if (a.gzip || a.raw || a.dict_len) a.bundle = 0u;
     hipError_t e = hipMemsetAsync(a.counter, 0, 8 * sizeof(uint32_t), stream);  // [0] stream index, [1] streams handed back, [3] the bundles' (pzg_bundle_kernel.h)
     if (e != hipSuccess) return e;
     if (a.bundle) {  // the small streams of the fixed code first, 64 of the launch order to a wave
@@ -222,10 +234,12 @@ hipError_t launch_inflate(const InflateArgs &a_in, int ring_bits, int num_cus, h
     // Ring size classes.  15: the whole 32 KiB DEFLATE window is an LDS ring (4 stream-waves per CU).
     // 12-14: a smaller near ring plus far back-references served from the stream's own flushed output
     // (more resident stream-waves per CU; the kernel is latency-bound, so that is what it scales with).
-    // (the gzip instances live in pzg_kernels_b.hip)
+    // (the gzip and the raw instances live in pzg_kernels_b.hip)
 #define PZG_LAUNCH_RING(RB)                                                                   \
     do {                                                                                      \
-        if (a.gzip)                                                                           \
+        if (a.raw)                                                                            \
+            e = launch_inflate_raw(a, RB, false, waves, stream);                              \
+        else if (a.gzip)                                                                      \
             e = launch_inflate_gzip(a, RB, false, waves, stream);                             \
         else                                                                                  \
             hipLaunchKernelGGL((inflate_kernel<RB, false, false>), grid, block, 0, stream, a); \
@@ -251,18 +265,22 @@ hipError_t launch_inflate(const InflateArgs &a_in, int ring_bits, int num_cus, h
         e = hipMemsetAsync(a.counter, 0, sizeof(uint32_t), stream);
         if (e != hipSuccess) return e;
         dim3 fgrid(a.n < 1024u ? a.n : 1024u);
-        if (a.gzip) {
-            e = launch_inflate_gzip(a, 15, true, fgrid.x, stream);
+        if (a.raw || a.gzip) {
+            e = a.raw ? launch_inflate_raw(a, 15, true, fgrid.x, stream) : launch_inflate_gzip(a, 15, true, fgrid.x, stream);
             if (e != hipSuccess) return e;
         } else
             hipLaunchKernelGGL((inflate_kernel<15, true, false>), fgrid, block, 0, stream, a);
     }
     e = hipGetLastError();
-    if (e != hipSuccess || !a.gzip) return e;
-    // gzip members: CRC-32 and ISIZE of every decoded stream against its trailer (one more pass over the output)
+    if (e != hipSuccess || !(a.gzip || a.raw == 2u)) return e;
+    // gzip members: CRC-32 and ISIZE of every decoded stream against its trailer (one more pass over the output); raw streams whose
+    // caller asked for the CRC-32: the same pass, reporting only
     const uint32_t cwg = (a.n + CRC_WAVES - 1u) / CRC_WAVES;
     dim3 cgrid(cwg < (uint32_t)num_cus * 8u ? cwg : (uint32_t)num_cus * 8u);
-    hipLaunchKernelGGL(crc32_verify_kernel, cgrid, dim3(64 * CRC_WAVES), 0, stream, a);
+    if (a.raw)
+        hipLaunchKernelGGL(crc32_report_kernel, cgrid, dim3(64 * CRC_WAVES), 0, stream, a);
+    else
+        hipLaunchKernelGGL(crc32_verify_kernel, cgrid, dim3(64 * CRC_WAVES), 0, stream, a);
     return hipGetLastError();
 }
 

@@ -32,6 +32,27 @@ hipError_t launch_inflate_gzip(const InflateArgs &a, int ring_bits, bool fixup, 
     return hipGetLastError();
 }
 
+// The raw instances (PZG_RAW).  Here and not beside the zlib instances by their code objects' notes (profiles/raw_kernel_notes.txt).
+hipError_t launch_inflate_raw(const InflateArgs &a, int ring_bits, bool fixup, uint32_t waves, hipStream_t stream)
+{
+    dim3 grid(waves), block(64);
+    if (fixup)
+        hipLaunchKernelGGL((inflate_raw_kernel<15, true>), grid, block, 0, stream, a);
+    else if (ring_bits == 15)
+        hipLaunchKernelGGL((inflate_raw_kernel<15, false>), grid, block, 0, stream, a);
+    else if (ring_bits == 14)
+        hipLaunchKernelGGL((inflate_raw_kernel<14, false>), grid, block, 0, stream, a);
+    else if (ring_bits == 13)
+        hipLaunchKernelGGL((inflate_raw_kernel<13, false>), grid, block, 0, stream, a);
+    else if (ring_bits == 12)
+        hipLaunchKernelGGL((inflate_raw_kernel<12, false>), grid, block, 0, stream, a);
+    else if (ring_bits == 11)
+        hipLaunchKernelGGL((inflate_raw_kernel<11, false>), grid, block, 0, stream, a);
+    else
+        return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------------
 // The resumable decoder (decompressIncremental, Monad.hs:163-197): one launch continues a batch of suspended decoders,
 // one wave each, as far as their new input and output room go.  Round 4: the small-ring instance (PZG_RES_RING = 12: 8 KiB

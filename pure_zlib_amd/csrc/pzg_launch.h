@@ -35,6 +35,9 @@ struct InflateArgs {
     // lane per stream, before the ordinary kernel takes what is left.  zlib streams without dictionaries only.
     uint32_t bundle;
     uint32_t *bundle_report;  // null, or a word of page-locked HOST memory: the launch's last kernel leaves 1 + the streams the bundles decoded there
+    // extension (PZG_RAW): 1 -- bare RFC 1951 streams, no header, no trailer, nothing checked (dictionaries apply unconditionally);
+    // 2 -- and adler[] gets the CRC-32 of the bytes delivered instead of their Adler-32 (PZG_CRC32: one more pass over the output)
+    uint32_t raw;
 };
 
 // one batched call of the resumable decoder (decompressIncremental): decoder i continues from its ResumeState
@@ -81,6 +84,8 @@ size_t inflate_strip_wave_bytes();  // ... one stream-wave's slice
 hipError_t launch_profile_switch(uint32_t *strip, uint32_t waves, bool off, hipStream_t stream);
 // the gzip instances (pzg_kernels_b.hip): `waves` workgroups of the ring's kernel, or of the fixup pass
 hipError_t launch_inflate_gzip(const InflateArgs &a, int ring_bits, bool fixup, uint32_t waves, hipStream_t stream);
+// the raw instances: the same
+hipError_t launch_inflate_raw(const InflateArgs &a, int ring_bits, bool fixup, uint32_t waves, hipStream_t stream);
 
 // partials: 3 * 4 * ceil(max_waves / 4) uint32 of device scratch
 hipError_t launch_adler32(const uint8_t *buf, uint64_t len, uint32_t init, uint32_t *partials, uint32_t max_waves,

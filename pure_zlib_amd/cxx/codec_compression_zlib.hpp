@@ -212,8 +212,10 @@ inline PinnedArena &arena(int which)
 // decompressMany: every stream decoded by its own wavefront in one launch.  zlib streams do not carry
 // their decoded size, so each stream gets a capacity (size_hint[i], or a guess) and the streams that
 // report PZG_E_OUT_TOO_SMALL are relaunched once with the exact size the kernel measured.
-inline std::vector<Either> decompressMany(const std::vector<LazyByteString> &inputs, Context &ctx = Context::shared(),
-                                          const std::vector<uint64_t> *size_hint = nullptr)
+// (container: 0 for zlib streams, PZG_RAW for bare RFC 1951 streams -- rawDecompressMany below)
+namespace detail {
+inline std::vector<Either> decompress_many(const std::vector<LazyByteString> &inputs, Context &ctx, const std::vector<uint64_t> *size_hint,
+                                           uint32_t container)
 {
     const size_t n = inputs.size();
     std::vector<Either> results(n);
@@ -253,7 +255,7 @@ inline std::vector<Either> decompressMany(const std::vector<LazyByteString> &inp
             if (in_len[k]) memcpy(in_p + in_off[k], flat[todo[k]].data(), in_len[k]);
         int rc = pzg_decompress_many(ctx.handle(), in_p, in_off.data(), in_len.data(), out_p, out_off.data(),
                                      out_cap.data(), out_len.data(), status.data(), det.data(), in_used.data(), adler.data(),
-                                     (uint32_t)m, pinned ? PZG_HOST_PINNED : 0u);
+                                     (uint32_t)m, container | (pinned ? PZG_HOST_PINNED : 0u));
         if (rc != PZG_RC_OK) throw std::runtime_error(std::string("pzg_decompress_many: ") + pzg_last_error(ctx.handle()));
         std::vector<size_t> retry;
         for (size_t k = 0; k < m; ++k) {
@@ -271,6 +273,23 @@ inline std::vector<Either> decompressMany(const std::vector<LazyByteString> &inp
     }
     return results;
 }
+}  // namespace detail
+
+inline std::vector<Either> decompressMany(const std::vector<LazyByteString> &inputs, Context &ctx = Context::shared(),
+                                          const std::vector<uint64_t> *size_hint = nullptr)
+{
+    return detail::decompress_many(inputs, ctx, size_hint, 0u);
+}
+
+// EXTENSION (the reference has no raw mode): the same over bare RFC 1951 streams -- what a deflated ZIP member holds, system zlib's
+// wbits = -15 (PZG_RAW, include/pzg.h): no header, no trailer, nothing checked; the same capacity guess and single relaunch, the
+// same Left values, "Finished with data remaining." for whole chunks behind the final block.
+inline std::vector<Either> rawDecompressMany(const std::vector<LazyByteString> &inputs, Context &ctx = Context::shared(),
+                                             const std::vector<uint64_t> *size_hint = nullptr)
+{
+    return detail::decompress_many(inputs, ctx, size_hint, PZG_RAW);
+}
+inline Either rawDecompress(const LazyByteString &ifile, Context &ctx = Context::shared()) { return rawDecompressMany({ifile}, ctx)[0]; }
 
 // Codec.Compression.Zlib.decompress (Zlib.hs:32-51): pure, strict, same Left values
 inline Either decompress(const LazyByteString &ifile, Context &ctx = Context::shared())

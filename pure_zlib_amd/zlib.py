@@ -218,9 +218,11 @@ class Context:
 
     # -- raw batched call on host memory ----------------------------------------------------------
     def decompress_many_raw(self, in_buf: np.ndarray, in_off, in_len, out_buf: np.ndarray, out_off, out_cap, gzip: bool = False,
-                            dict_buf: Optional[np.ndarray] = None, dict_off=None, dict_len=None, pinned: bool = False):
+                            dict_buf: Optional[np.ndarray] = None, dict_off=None, dict_len=None, pinned: bool = False,
+                            raw: bool = False, crc32: bool = False):
         """Thin wrapper of pzg_decompress_many on host numpy buffers.
         pinned: in_buf / out_buf are page-locked arenas (pinned_array) with ascending extents -- PZG_HOST_PINNED.
+        raw: the streams are bare RFC 1951 (PZG_RAW); crc32 (with raw only): adler holds the CRC-32 of what was delivered (PZG_CRC32).
         Returns (out_len u64[n], status i32[n], detail u32[n,2], in_used u64[n], adler u32[n])."""
         in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
         in_len = np.ascontiguousarray(in_len, dtype=np.uint64)
@@ -234,6 +236,7 @@ class Context:
         adler = np.zeros(n, dtype=np.uint32)
         if n == 0:
             return out_len, status, detail, in_used, adler
+        container = (_ffi.GZIP if gzip else 0) | (_ffi.RAW if raw else 0) | (_ffi.CRC32 if crc32 else 0)
         if dict_buf is not None:  # extension: one preset dictionary extent per stream (length 0 = none)
             if gzip:  # (preset dictionaries are a zlib-container notion: the C ABI rejects the combination too)
                 raise ValueError("gzip=True and preset dictionaries cannot be combined")
@@ -242,26 +245,28 @@ class Context:
             rc = self._L.pzg_decompress_many_dict(
                 self._h, in_buf.ctypes.data, in_off.ctypes.data, in_len.ctypes.data, dict_buf.ctypes.data, dict_off.ctypes.data,
                 dict_len.ctypes.data, out_buf.ctypes.data, out_off.ctypes.data, out_cap.ctypes.data, out_len.ctypes.data,
-                status.ctypes.data, detail.ctypes.data, in_used.ctypes.data, adler.ctypes.data, n, 0)
+                status.ctypes.data, detail.ctypes.data, in_used.ctypes.data, adler.ctypes.data, n, container)
             _ffi.check(rc, self._h)
             return out_len, status, detail, in_used, adler
         rc = self._L.pzg_decompress_many(
             self._h, in_buf.ctypes.data, in_off.ctypes.data, in_len.ctypes.data, out_buf.ctypes.data,
             out_off.ctypes.data, out_cap.ctypes.data, out_len.ctypes.data, status.ctypes.data, detail.ctypes.data,
-            in_used.ctypes.data, adler.ctypes.data, n, (_ffi.GZIP if gzip else 0) | (_ffi.HOST_PINNED if pinned else 0))
+            in_used.ctypes.data, adler.ctypes.data, n, container | (_ffi.HOST_PINNED if pinned else 0))
         _ffi.check(rc, self._h)
         return out_len, status, detail, in_used, adler
 
     # -- device-pointer call (the timed path; pointers are raw integers) ----------------------------
     def decompress_many_device(self, in_base: int, in_off: int, in_len: int, out_base: int, out_off: int,
                                out_cap: int, out_len: int, status: int, detail: int, in_used: int, adler: int,
-                               n: int, sync: bool = True, gzip: bool = False, lpt: bool = False):
+                               n: int, sync: bool = True, gzip: bool = False, lpt: bool = False, raw: bool = False, crc32: bool = False):
         flags = _ffi.DEVICE_PTRS | (0 if sync else _ffi.ASYNC) | (_ffi.GZIP if gzip else 0) | (_ffi.LPT_ORDER if lpt else 0)
+        flags |= (_ffi.RAW if raw else 0) | (_ffi.CRC32 if crc32 else 0)
         rc = self._L.pzg_decompress_many(self._h, in_base, in_off, in_len, out_base, out_off, out_cap, out_len,
                                          status, detail or None, in_used or None, adler or None, n, flags)
         _ffi.check(rc, self._h)
 
-    def decompress_many_sharded(self, batches, sync: bool = True, gzip: bool = False, lpt: bool = False):
+    def decompress_many_sharded(self, batches, sync: bool = True, gzip: bool = False, lpt: bool = False, raw: bool = False,
+                                crc32: bool = False):
         """pzg_decompress_many_sharded: `batches` is a list of dicts (shard, n, in_base, in_off, in_len, out_base, out_off,
         out_cap, out_len, status and optionally detail, in_used, adler), every pointer an integer address of device memory
         on that shard's device.  One call enqueues them all; nothing leaves the devices."""
@@ -270,6 +275,7 @@ class Context:
             for k, _t in _ffi.DeviceBatch._fields_:
                 setattr(q, k, b.get(k) or 0)
         flags = (0 if sync else _ffi.ASYNC) | (_ffi.GZIP if gzip else 0) | (_ffi.LPT_ORDER if lpt else 0)
+        flags |= (_ffi.RAW if raw else 0) | (_ffi.CRC32 if crc32 else 0)
         _ffi.check(self._L.pzg_decompress_many_sharded(self._h, C.byref(arr) if len(batches) else None, len(batches), flags), self._h)
 
     def adler32(self, data, init: int = 1) -> int:
@@ -370,11 +376,17 @@ def decompress_many(streams: Sequence[LazyByteString], ctx: Optional[Context] = 
 
     zdict (EXTENSION, the reference skips DICTID: Zlib.hs:68): one preset dictionary per stream (None = none); a stream
     whose header has FDICT set then decodes with it as history, as zlib.decompressobj(zdict=...) does."""
+    return _decompress_many(streams, ctx, size_hint, gzip, zdict)[0]
+
+
+def _decompress_many(streams, ctx, size_hint, gzip, zdict, raw=False, crc32=False):
+    """The body of decompress_many and raw_decompress_many: (results, checksums) -- the library's adler[] word of every Right."""
     ctx = ctx or default_context()
     chunked = [_to_chunks(s) for s in streams]
     flat = [b"".join(c) for c in chunked]
     n = len(flat)
     results: List[Optional[Either]] = [None] * n
+    sums: List[Optional[int]] = [None] * n
     # without a hint: a modest first guess (the batch is packed, so small guesses cost little); PZG_E_OUT_TOO_SMALL
     # streams come back with their exact size and are relaunched once
     caps = [int(size_hint[i]) if size_hint is not None else max(256, 4 * len(flat[i])) for i in range(n)]
@@ -410,21 +422,22 @@ def decompress_many(streams: Sequence[LazyByteString], ctx: Optional[Context] = 
             do[1:] = np.cumsum(dl[:-1])
             db = np.frombuffer(b"".join((zdict[i] or b"") for i in todo) + b"\0" * 16, dtype=np.uint8)
             dict_args = dict(dict_buf=db, dict_off=do, dict_len=dl)
-        out_len, status, detail, in_used, _adler = ctx.decompress_many_raw(in_buf, in_off, in_len, out_buf, out_off, out_cap, gzip,
-                                                                           pinned=pinned, **dict_args)
+        out_len, status, detail, in_used, adler = ctx.decompress_many_raw(in_buf, in_off, in_len, out_buf, out_off, out_cap, gzip,
+                                                                          pinned=pinned, raw=raw, crc32=crc32, **dict_args)
         retry = []
         for k, i in enumerate(todo):
             st = int(status[k])
             if st == _ffi.OK:
                 data = out_buf[int(out_off[k]):int(out_off[k]) + int(out_len[k])].tobytes()
                 results[i] = _apply_chunk_rule(chunked[i], int(in_used[k]), data)
+                sums[i] = int(adler[k])
             elif st == _ffi.E_OUT_TOO_SMALL and _attempt == 0:
                 caps[i] = int(out_len[k])
                 retry.append(i)
             else:
                 results[i] = Left(error_from_status(flat[i], st, detail[k]))
         todo = retry
-    return results  # type: ignore[return-value]
+    return results, sums
 
 
 def _apply_chunk_rule(chunks: List[bytes], in_used: int, data: bytes) -> Either:
@@ -457,6 +470,23 @@ def gzip_decompress_many(streams: Sequence[LazyByteString], ctx: Optional[Contex
     """EXTENSION (the reference lists gzip as a TODO): decompress_many over RFC 1952
     members -- same DEFLATE kernel, gzip header, CRC-32 + ISIZE trailer verified on the device."""
     return decompress_many(streams, ctx, size_hint, gzip=True)
+
+
+def raw_decompress_many(streams: Sequence[LazyByteString], size_hint: Optional[Sequence[int]] = None, crc32: bool = False,
+                        dicts: Optional[Sequence[Optional[bytes]]] = None, ctx: Optional[Context] = None):
+    """EXTENSION: decompress_many over bare RFC 1951 streams (PZG_RAW) -- what a deflated ZIP member holds, system zlib's
+    wbits = -15: no header, no trailer, nothing checked.  The same capacity guess and single relaunch, the same errors, and
+    "Finished with data remaining." for whole chunks behind the final block.  dicts: one dictionary per stream (None = none),
+    the history in front of the stream's output as zlib.decompressobj(-15, zdict=...) has it.
+    crc32=True: returns (results, crcs) -- crcs[i] is the CRC-32 (RFC 1952) of stream i's bytes, computed on the device and
+    checked against nothing (None for a Left); the caller owns the expected value."""
+    results, sums = _decompress_many(streams, ctx, size_hint, False, dicts, raw=True, crc32=crc32)
+    return (results, sums) if crc32 else results
+
+
+def raw_decompress(data: LazyByteString, ctx: Optional[Context] = None, size_hint: Optional[int] = None) -> Either:
+    """decompress over one bare RFC 1951 stream (see raw_decompress_many)."""
+    return raw_decompress_many([data], None if size_hint is None else [size_hint], ctx=ctx)[0]
 
 
 # Haskell-cased aliases so call sites read like the reference
