@@ -228,6 +228,9 @@ hipError_t launch_inflate(const InflateArgs &a_in, int ring_bits, int num_cus, h
 #if defined(PZG_LAB) && defined(PZG_LAB_BUNDLE_NOFLAG)  // (lab: what the bundle kernel's mere presence costs the kernel behind it)
         a.bundle = 0u;
 #endif
+#if defined(PZG_LAB) && defined(PZG_LAB_BUNDLES_ONLY)  // (lab: the lanes' own results -- what they did not decode keeps ST_BUNDLE_TODO, tests/test_gpu_bundle_edges.py)
+        return hipSuccess;
+#endif
     }
     const uint32_t waves = launch_waves(ring_bits, num_cus, a.n, a.gzip);
     dim3 grid(waves), block(64);

@@ -128,6 +128,16 @@ def test_lab_library_with_seeded_profiles_builds():
     assert b"hipv4-amdgcn-amd-amdhsa--gfx950" in open(so, "rb").read()
 
 
+BUNDLESONLY_FLAGS = ["-DPZG_LAB", "-DPZG_LAB_BUNDLES_ONLY"]  # a launch ends behind the bundle kernel: what no lane decoded keeps status 103
+
+
+def test_lab_library_that_stops_behind_the_bundles_builds():
+    """build/lab_bundlesonly/libpzg.so (for tests/test_gpu_bundle_edges.py::test_lanes_alone_decode_what_the_model_calls_clean) builds
+    here and travels to the GPU box with the snapshot."""
+    so = lab_library("bundlesonly", BUNDLESONLY_FLAGS)
+    assert b"hipv4-amdgcn-amd-amdhsa--gfx950" in open(so, "rb").read()
+
+
 def test_lab_library_with_failing_guesses_builds():
     """build/lab_poor/libpzg.so (the device build of the same experiment, for tests/test_gpu_parity.py) builds here, carries a
     gfx950 code object, and travels to the GPU box with the snapshot."""
