@@ -89,6 +89,7 @@ extern "C" {
 /* pzg_decompress_many_dict only (extension): */
 #define PZG_E_DICT               20  /* "Header error: preset dictionary mismatch: <hex d0> != <hex d1>": the stream's DICTID (d0) is
                                       * not the Adler-32 of the dictionary supplied for it (d1) */
+#define PZG_E_SEGMENT 21  /* segments only: the blocks do not end at end_bit. d0 = 1 final block came first, 2 a block ran past; d1 = bit reached */
 /* Reference raise sites that have NO status because they cannot fire (here or in the reference):
  *   Deflate.hs:150-151  DecompressionError "Unexpected code: <n>" -- getCodeLengths' fall-through for a code-length symbol outside
  *                       0..18; the code-length alphabet has exactly 19 symbols (Deflate.hs:87-88 builds its tree from 19 lengths),
@@ -299,6 +300,59 @@ PZG_API int pzg_decompress_many_dict(pzg_ctx *ctx,
                              uint64_t *out_len, int32_t *status, uint32_t *detail,
                              uint64_t *in_used, uint32_t *adler,
                              uint32_t n, uint32_t flags);
+
+/*
+ * EXTENSION -- one LARGE stream, indexed (the zran / indexed_gzip scheme).  A stream is decoded by one wavefront; an index of
+ * access points cuts it into segments that are independent pieces of work, so that the whole stream decodes with a wavefront per
+ * segment and any byte range is read without decoding what is in front of it.  An access point is a block boundary: the block
+ * that starts at bit in_bit of the raw stream (counted from bit 0 of its first byte) produces output byte out_pos first; with the
+ * 32768 bytes of output in front of out_pos (its window) it is all a decoder needs to start there.
+ *
+ * pzg_index_build: one sequential decode of ONE raw (RFC 1951) stream -- out, out_len, status, detail, in_used and adler are exactly
+ * what pzg_decompress_many gives with PZG_RAW, which is implied -- that also records the points.  The rule: the end of a non-final
+ * block is a point when out_pos is `span` bytes or more past the last point's out_pos (past 0 for the first point); span 0 means
+ * 1 MiB.  *npoints is the number of points the stream HAS at this span: if it exceeds max_points only the first max_points were
+ * stored (their windows too) and the caller repeats with more room or a larger span.  The points (and windows) are valid only
+ * when *status == PZG_OK.  windows (max_points x 32768 bytes, or NULL): slot k receives the window of point k at its END -- the
+ * last min(out_pos, 32768) bytes of the slot; what lies in front of them in the slot is left as it was.
+ * flags: 0 -- in, out, points and windows are host memory; PZG_DEVICE_PTRS -- they are device memory.  npoints, out_len, status,
+ * detail, in_used and adler are host memory in both forms, and the call returns when they are filled in: it runs on a stream of
+ * the library's own, NOT the one given to pzg_set_stream, and is ordered against the caller's other work only by returning -- work
+ * the caller has enqueued on a stream of its own that writes `in` must have finished before the call.  PZG_GZIP, PZG_HOST_PINNED,
+ * any other flag, and a context of several devices are PZG_RC_BAD_ARG.
+ *
+ * pzg_decompress_many_segments: pzg_decompress_many_dict over PZG_RAW (implied) pieces that begin and end inside a stream.  Segment i
+ * is the bytes in_off[i] .. + in_len[i]; its first block's header starts at bit start_bit[i] (0..7) of the first of them, and it ends
+ * with the block that ends at bit end_bit[i], counted from bit 0 of that same byte -- whatever that block's BFINAL says -- or, with
+ * end_bit[i] = 0, with the final block, as a raw stream does.  Bit offsets reported for the segment (end_bit, detail[1] of
+ * PZG_E_HUFF_BUILD) count the same way.  No trailer is read; in_used[i] is the byte that holds bit end_bit[i] - 1, plus one.
+ * dict_* (required) is the window of each segment (dict_len[i] = 0: none, for the segment at the start of the stream).
+ *   status[i]   PZG_E_SEGMENT: a block ended past end_bit[i] (d0 = 2), or the final block ended before it (d0 = 1); d1 = the bit reached.
+ *               A segment cannot tell a wrong window from the right one: the caller checks the checksums.
+ *   failed and over-capacity segments follow the rules of pzg_decompress_many: out_len, the bytes delivered, the checksum, nothing
+ *   written past out_cap[i].  adler[i] covers the segment's own bytes, starting from 1 (PZG_CRC32: their CRC-32) -- combine them
+ *   with adler32_combine / crc32_combine.
+ * Segments always decode on the 32 KiB ring (a window is history on that ring only), whatever PZG_OPT_RING_BITS says.
+ * flags: PZG_DEVICE_PTRS, PZG_ASYNC, PZG_LPT_ORDER, PZG_CRC32.  PZG_GZIP, PZG_HOST_PINNED and a context of several devices are
+ * PZG_RC_BAD_ARG; so, with host pointers, are start_bit[i] > 7 and end_bit[i] > 8 * in_len[i] (device arrays are not read by the host:
+ * such a segment simply starts where it is told and fails where its input ends).
+ */
+typedef struct pzg_index_point { uint64_t in_bit, out_pos; } pzg_index_point;
+
+PZG_API int pzg_index_build(pzg_ctx *ctx, const uint8_t *in, uint64_t in_len,
+        uint8_t *out, uint64_t out_cap, uint64_t span,          /* span 0: 1 MiB */
+        pzg_index_point *points, uint32_t max_points, uint32_t *npoints,
+        uint8_t *windows,                                       /* max_points x 32768 bytes, or NULL */
+        uint64_t *out_len, int32_t *status, uint32_t detail[2], uint64_t *in_used, uint32_t *adler,
+        uint32_t flags);                                        /* PZG_DEVICE_PTRS or 0; PZG_RAW implied */
+
+PZG_API int pzg_decompress_many_segments(pzg_ctx *ctx,
+        const uint8_t *in_base, const uint64_t *in_off, const uint64_t *in_len,
+        const uint8_t *start_bit, const uint64_t *end_bit,
+        const uint8_t *dict_base, const uint64_t *dict_off, const uint64_t *dict_len,
+        uint8_t *out_base, const uint64_t *out_off, const uint64_t *out_cap,
+        uint64_t *out_len, int32_t *status, uint32_t *detail, uint64_t *in_used, uint32_t *adler,
+        uint32_t n, uint32_t flags);   /* PZG_DEVICE_PTRS, PZG_ASYNC, PZG_LPT_ORDER, PZG_CRC32; PZG_RAW implied */
 
 /*
  * decompressIncremental / ZlibDecoder (Zlib.hs:3-8, Monad.hs:163-197; driver Deflate.hs:30-48), batched: a pzg_decoder

@@ -8,6 +8,7 @@ Only what the hot path needs lives here:
   incremental.py, deflate_cli.py, benchmark.py   the reference's streaming protocol, CLI and criterion harness
              over the same path; gzip members (row 4) are `gzip_decompress_many`
   zip.py     ZIP archives read and tested in one launch (raw DEFLATE members, sizes and CRC-32s from the central directory)
+  indexed.py ONE large stream: an index of access points, every segment its own wavefront, reads at any offset
   cxx/       the same module mirror in C++ (header-only)
 
 There is no CPU fallback: importing works anywhere, computing needs libpzg.so and a gfx950 device.
@@ -18,3 +19,4 @@ from .zlib import (  # noqa: F401
     HuffmanTreeError, Left, Right, adler32, decompress, decompress_many, decompressMany, default_context,
     gzip_decompress_many, raw_decompress, raw_decompress_many,
 )
+from .indexed import Index, adler32_combine, crc32_combine  # noqa: F401

@@ -119,6 +119,7 @@ enum : int32_t {
     ST_GZIP_HEADER = 18,  // extension (RFC 1952): detail0 = 1 magic, 2 method, 3 reserved flag bits, 4 header CRC16
     ST_GZIP_ISIZE = 19,   // extension: detail0 = ISIZE in the trailer, detail1 = bytes produced mod 2^32
     ST_DICT = 20,         // extension (PZG_FDICT): detail0 = DICTID of the stream, detail1 = Adler-32 of the dictionary supplied
+    ST_SEGMENT = 21,      // extension (segments of an indexed stream): the blocks do not end at end_bit; detail0 = 1 the final block came first, 2 a block ran past it; detail1 = the bit reached
     ST_NEED_INPUT = 101,  // resumable decoder: every complete token of the input so far has been decoded; more input is needed
     ST_OUT_FULL = 102,    // resumable decoder: the output room of this call is used up; call again with what is left of the input
     ST_RETRY_FULL_RING = 100,  // internal: a small-ring launch met an output larger than its capacity; the 32 KiB ring kernel redoes the stream
@@ -266,6 +267,12 @@ struct StreamResult {
     uint32_t gz_crc;   // gzip only: the CRC-32 the output must have according to the members' trailers
     uint64_t out_len;
     uint64_t in_used;
+};
+
+// an access point of an indexed stream (include/pzg.h pzg_index_point): a block starts at bit in_bit of the stream and its first byte is
+// produced byte out_pos
+struct IndexPoint {
+    uint64_t in_bit, out_pos;
 };
 
 // ---- resumable decoding (decompressIncremental, Monad.hs:163-197): what a suspended decoder keeps in HBM -------
@@ -487,9 +494,12 @@ struct BitReader {
 // RES: the resumable instance (decompressIncremental): suspends when the input or the output room runs out
 // RAW: the streams are bare RFC 1951 (an extension: what a ZIP member holds): no header, no trailer, nothing checked; its own kernel
 // instances again (pzg_inflate_kernel.h inflate_raw_kernel)
-template <int RING_BITS, bool GZIP = false, bool RES = false, bool RAW = false>
+// SEG: a raw decoder for the pieces of ONE indexed stream (an extension; pzg_kernels_b.hip inflate_seg_kernel): it starts at a bit
+// inside its first byte, may stop at the end of a block that is not the final one, and can record access points as it goes
+template <int RING_BITS, bool GZIP = false, bool RES = false, bool RAW = false, bool SEG = false>
 struct Decoder {
     static_assert(!RAW || (!GZIP && !RES), "a raw stream has no container and no resumable instance");
+    static_assert(!SEG || RAW, "segments are pieces of a raw stream");
     static constexpr uint32_t RING = 1u << RING_BITS;
     static constexpr uint32_t RMASK = RING - 1u;
     static constexpr uint32_t FLUSH_AT = RING - 1024u;
@@ -552,6 +562,12 @@ struct Decoder {
     uint64_t in_total_bits;     // 8 * the input bytes consumed by earlier calls
     uint32_t qn;                // tokens waiting in QT (lanes 0..qn-1, never more than QCAP), see queue_append()
     LaneVec<uint32_t> QT;
+    // SEG only (set by the caller before run(); bit offsets count from bit 0 of the input's first byte)
+    uint32_t seg_start;         // the first block's header starts at this bit (0..7)
+    uint64_t seg_end;           // the segment ends with the block that ends at this bit; 0: with the final block
+    IndexPoint *idx_points;     // access points are recorded here (idx_span != 0), the first idx_cap of them
+    uint32_t idx_cap, idx_n;    // idx_n: the points the stream has so far, stored or not
+    uint64_t idx_span, idx_last;  // a non-final block's end is a point once `op` is idx_span or more past the last point's (past 0 at first)
 #if defined(PZG_PROFILE)
     uint64_t prof[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // 0 total, 1 header+tables, 2 token loop, 3 flush, 4 window_append, 5 checked steps, 6 windows, 7 tokens queued, 8-11 emit phases, 12 emit, 13 segments, 14 general copies, 15 checked steps
 #endif
@@ -596,6 +612,13 @@ struct Decoder {
         qn = uni(qn);
         in_byte0 = uni64(in_byte0);
         status = (int32_t)uni((uint32_t)status);
+        if constexpr (SEG) {
+            seg_end = uni64(seg_end);
+            idx_n = uni(idx_n);
+            idx_cap = uni(idx_cap);
+            idx_span = uni64(idx_span);
+            idx_last = uni64(idx_last);
+        }
 #endif
     }
 
@@ -1707,7 +1730,7 @@ struct Decoder {
         return stopper;
     }
 
-    // Place and produce the bytes of the queue's leading tokens.  A segment is at most SEG = 128 output bytes, produced
+    // Place and produce the bytes of the queue's leading tokens.  A segment is at most SEG_BYTES = 128 output bytes, produced
     // in two passes of 64 (lane j: bytes j and 64 + j); the work per token is paid once for both.
     // Token lanes learn their output offset from a prefix sum of their lengths and announce themselves at that offset
     // (one crossbar scatter per pass); counting the announcements up to its own position tells every output lane which
@@ -1716,7 +1739,7 @@ struct Decoder {
     // before the segment starts (dist < offset + len) or lies before the output (dist > produced + offset).  A match
     // that heads a segment and still does not fit overlaps its own output or is longer than the segment: copy_match()
     // takes it.  Precondition: qn != 0.
-    static constexpr uint32_t SEG = 128u;
+    static constexpr uint32_t SEG_BYTES = 128u;
 
     // one pass of a segment, the gather: VAL = the byte of output offset o = 64 * pass + lane (from its literal token or
     // the near ring), FARM = the lanes whose source is older than the ring; DIST = their tokens' distances.
@@ -1848,7 +1871,7 @@ struct Decoder {
             const uint32_t tk = PZG_LV(QT, t), lout = (tk >> 16) & 511u, dist = tk & 0xffffu;
             const uint32_t endb = PZG_LV(INCL, t), start = endb - lout;
             PZG_LV(START, t) = start;
-            PZG_LV(BIG, t) = endb > SEG;                 // does not fit the segment
+            PZG_LV(BIG, t) = endb > SEG_BYTES;             // does not fit the segment
             PZG_LV(MATCH, t) = (int32_t)tk < 0;
             PZG_LV(SRC_IN, t) = dist < endb;              // a match whose source is not complete before the segment starts
             PZG_LV(SRC_OUT, t) = dist > hist + start;     // ... or lies before the output (an error: found when it heads a segment)
@@ -4152,6 +4175,11 @@ struct Decoder {
 #endif
         set_far_base();
         br.start(in, in_len, 0);
+        if constexpr (SEG) {
+            br.drop(seg_start);  // (stream_bit_pos() goes on counting from bit 0 of the first byte: stored_block()'s byte arithmetic holds)
+            idx_n = 0;
+            idx_last = 0;
+        }
         PZG_T0(tall);
         // the reader indexes dwords with 32 bits: 16 GiB per stream (include/pzg.h).  (Tested on the high word: a 64-bit
         // compare is a vector instruction whose constant would sit in a vector-register pair for the whole kernel.)
@@ -4396,6 +4424,22 @@ struct Decoder {
                 PZG_ACC(2, tt);
             }
             if (st != ST_OK) return st;
+            if constexpr (SEG) {
+                const uint64_t at = stream_bit_pos();
+                if (seg_end != 0u) {
+                    if (at == seg_end) return ST_OK;  // (whatever BFINAL said: the index knows where its segments end)
+                    if (at > seg_end) return fail(ST_SEGMENT, 2, (uint32_t)at);
+                    if (bfinal) return fail(ST_SEGMENT, 1, (uint32_t)at);
+                }
+                if (!bfinal && idx_span != 0u && op - idx_last >= idx_span) {
+                    if (idx_n < idx_cap && (lane_id() == 0u || PZG_WAVE == 1u)) {  // (one lane, plain vector stores)
+                        idx_points[idx_n].in_bit = at;
+                        idx_points[idx_n].out_pos = op;
+                    }
+                    idx_n += 1u;
+                    idx_last = op;
+                }
+            }
             if (bfinal) return ST_OK;
         }
     }

@@ -883,8 +883,9 @@ int host_path(pzg_ctx *ctx, Shard &sh, const HostBatch &b, const uint32_t *idx, 
 }
 
 // ---- preset dictionaries (extension): a plain synchronous path on lane 0 -- pack, upload, launch, download ----------
+// (segments of an indexed stream, pzg_decompress_many_segments: start_bit / end_bit travel along -- null otherwise)
 int dict_path(pzg_ctx *ctx, Shard &sh, const HostBatch &b, const uint8_t *dict_base, const uint64_t *dict_off, const uint64_t *dict_len,
-              uint32_t n)
+              uint32_t n, const uint8_t *start_bit = nullptr, const uint64_t *end_bit = nullptr)
 {
     Lane &ln = sh.lanes[0];
     std::lock_guard<std::mutex> lk(ln.mu);
@@ -912,10 +913,14 @@ int dict_path(pzg_ctx *ctx, Shard &sh, const HostBatch &b, const uint8_t *dict_b
     }
     if ((rc = arena_reserve(ctx, ln.d_in[0], ip + 64)) != PZG_RC_OK) return rc;
     if ((rc = arena_reserve(ctx, ln.d_out[0], op + 64)) != PZG_RC_OK) return rc;
-    if ((rc = arena_reserve(ctx, ln.d_meta[0], 80 * (size_t)n + 64)) != PZG_RC_OK) return rc;
+    if ((rc = arena_reserve(ctx, ln.d_meta[0], 96 * (size_t)n + 64)) != PZG_RC_OK) return rc;  // (80 n, and a segment's end_bit | start_bit)
     uint8_t *dm = (uint8_t *)ln.d_meta[0].p;
     hipStream_t st = ln.s_k;
     HIP_TRY(ctx, hipMemcpyAsync(dm, meta.data(), 48 * (size_t)n, hipMemcpyHostToDevice, st));
+    if (start_bit) {
+        HIP_TRY(ctx, hipMemcpyAsync(dm + 80 * (size_t)n, end_bit, 8 * (size_t)n, hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemcpyAsync(dm + 88 * (size_t)n, start_bit, (size_t)n, hipMemcpyHostToDevice, st));
+    }
     HIP_TRY(ctx, hipMemcpyAsync(ln.d_in[0].p, hin.data(), ip, hipMemcpyHostToDevice, st));
     pzg::InflateArgs a{};
     a.in_base = (const uint8_t *)ln.d_in[0].p;
@@ -935,12 +940,27 @@ int dict_path(pzg_ctx *ctx, Shard &sh, const HostBatch &b, const uint8_t *dict_b
     a.n = n;
     a.counter = ln.d_counter;
     a.raw = raw_mode(b.flags);  // (raw streams: the dictionary is the history, whatever the stream says)
+    if (start_bit) {
+        a.seg = 1u;
+        a.seg_end_bit = (const uint64_t *)(dm + 80 * (size_t)n);
+        a.seg_start_bit = dm + 88 * (size_t)n;
+    }
     strip_for_launch(ctx, ln.d_strip, sh.num_cus, n, 0u, a);
+    HIP_TRY(ctx, hipEventRecord(ln.ev_t0, st));
     HIP_TRY(ctx, pzg::launch_inflate(a, ctx->ring_bits, sh.num_cus, st));
+    HIP_TRY(ctx, hipEventRecord(ln.ev_t1, st));
     std::vector<uint8_t> res(32 * (size_t)n), hout(op + 16);
     HIP_TRY(ctx, hipMemcpyAsync(res.data(), dm + 48 * (size_t)n, 32 * (size_t)n, hipMemcpyDeviceToHost, st));
     if (op) HIP_TRY(ctx, hipMemcpyAsync(hout.data(), ln.d_out[0].p, op, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
+    {   // the call's kernel span (pzg_last_kernel_ms), as host_path records it
+        float ms = -1.0f;
+        const bool ok = hipEventElapsedTime(&ms, ln.ev_t0, ln.ev_t1) == hipSuccess;
+        std::lock_guard<std::mutex> g(sh.mu);
+        sh.host_ms = ok ? (double)ms : -1.0;
+        sh.last_was_host = true;
+        sh.timed = true;
+    }
     const uint64_t *olen = (const uint64_t *)res.data(), *used = olen + n;
     const int32_t *stt = (const int32_t *)(used + n);
     const uint32_t *ad = (const uint32_t *)(stt + n), *det = ad + n;
@@ -1267,6 +1287,171 @@ int pzg_decompress_many_dict(pzg_ctx *ctx, const uint8_t *in_base, const uint64_
             ctx->last_error = "C++ exception inside pzg_decompress_many";
         }
         return PZG_RC_HIP_ERROR;
+    }
+}
+
+int pzg_decompress_many_segments(pzg_ctx *ctx, const uint8_t *in_base, const uint64_t *in_off, const uint64_t *in_len,
+                                 const uint8_t *start_bit, const uint64_t *end_bit, const uint8_t *dict_base, const uint64_t *dict_off,
+                                 const uint64_t *dict_len, uint8_t *out_base, const uint64_t *out_off, const uint64_t *out_cap,
+                                 uint64_t *out_len, int32_t *status, uint32_t *detail, uint64_t *in_used, uint32_t *adler, uint32_t n,
+                                 uint32_t flags)
+{
+    if (!ctx_live(ctx)) return PZG_RC_BAD_ARG;
+    if (flags & ~(PZG_DEVICE_PTRS | PZG_ASYNC | PZG_LPT_ORDER | PZG_CRC32 | PZG_RAW)) return PZG_RC_BAD_ARG;  // (PZG_GZIP, PZG_HOST_PINNED: no)
+    flags |= PZG_RAW;
+    if (ctx->shards.size() != 1) return PZG_RC_BAD_ARG;
+    if ((flags & PZG_ASYNC) && !(flags & PZG_DEVICE_PTRS)) return PZG_RC_BAD_ARG;
+    if (n == 0) return PZG_RC_OK;
+    if (!in_base || !in_off || !in_len || !start_bit || !end_bit || !out_off || !out_cap || !out_len || !status) return PZG_RC_BAD_ARG;
+    if (!dict_base || !dict_off || !dict_len) return PZG_RC_BAD_ARG;
+    try {
+        if (flags & PZG_DEVICE_PTRS) {
+            if (!out_base) return PZG_RC_BAD_ARG;
+            pzg::InflateArgs a{};
+            a.in_base = in_base;
+            a.in_off = in_off;
+            a.in_len = in_len;
+            a.out_base = out_base;
+            a.out_off = out_off;
+            a.out_cap = out_cap;
+            a.out_len = out_len;
+            a.status = status;
+            a.detail = detail;
+            a.in_used = in_used;
+            a.adler = adler;
+            a.n = n;
+            a.dict_base = dict_base;
+            a.dict_off = dict_off;
+            a.dict_len = dict_len;
+            a.seg = 1u;
+            a.seg_start_bit = start_bit;
+            a.seg_end_bit = end_bit;
+            return launch_device(ctx, *ctx->shards[0], a, flags);
+        }
+        bool any_out = false;
+        for (uint32_t i = 0; i < n; ++i) {
+            if (in_off[i] + in_len[i] < in_off[i] || out_off[i] + out_cap[i] < out_off[i]) return PZG_RC_BAD_ARG;
+            if ((in_len[i] >> 40) || (out_cap[i] >> 40)) return PZG_RC_BAD_ARG;
+            if (dict_off[i] + dict_len[i] < dict_off[i] || (dict_len[i] >> 32)) return PZG_RC_BAD_ARG;
+            if (start_bit[i] > 7u || end_bit[i] > 8u * in_len[i]) return PZG_RC_BAD_ARG;
+            any_out |= out_cap[i] != 0;
+        }
+        if (any_out && !out_base) return PZG_RC_BAD_ARG;
+        HostBatch b{in_base, in_off, in_len, out_base, out_off, out_cap, out_len, status, detail, in_used, adler, flags};
+        return dict_path(ctx, *ctx->shards[0], b, dict_base, dict_off, dict_len, n, start_bit, end_bit);
+    } catch (const std::bad_alloc &) {
+        return PZG_RC_NO_MEMORY;
+    }
+}
+
+int pzg_index_build(pzg_ctx *ctx, const uint8_t *in, uint64_t in_len, uint8_t *out, uint64_t out_cap, uint64_t span, pzg_index_point *points,
+                    uint32_t max_points, uint32_t *npoints, uint8_t *windows, uint64_t *out_len, int32_t *status, uint32_t detail[2],
+                    uint64_t *in_used, uint32_t *adler, uint32_t flags)
+{
+    if (!ctx_live(ctx)) return PZG_RC_BAD_ARG;
+    if (flags & ~(PZG_DEVICE_PTRS | PZG_RAW)) return PZG_RC_BAD_ARG;
+    if (ctx->shards.size() != 1) return PZG_RC_BAD_ARG;
+    if (!in || !npoints || !out_len || !status || (out_cap && !out) || (max_points && !points)) return PZG_RC_BAD_ARG;
+    if ((in_len >> 34) || (out_cap >> 40)) return PZG_RC_BAD_ARG;
+    if (span == 0) span = 1ull << 20;
+    const bool dev = (flags & PZG_DEVICE_PTRS) != 0;
+    Shard &sh = *ctx->shards[0];
+    Lane &ln = sh.lanes[0];
+    try {
+        std::lock_guard<std::mutex> lk(ln.mu);
+        HIP_TRY(ctx, hipSetDevice(sh.device));
+        int rc = lane_prepare(ctx, ln);
+        if (rc != PZG_RC_OK) return rc;
+        hipStream_t st = ln.s_k;
+        // device side: the input, then out | points | windows in one arena (host pointers), and 128 bytes of arguments and results
+        const uint8_t *d_in = in;
+        uint8_t *d_out = out, *d_win = windows;
+        uint64_t *d_pts = (uint64_t *)points;
+        const size_t pts_off = pad256(out_cap), win_off = pts_off + pad256(16 * (size_t)max_points);
+        if (!dev) {
+            if ((rc = arena_reserve(ctx, ln.d_in[0], in_len + 64)) != PZG_RC_OK) return rc;
+            if ((rc = arena_reserve(ctx, ln.d_out[0], win_off + (windows ? 32768 * (size_t)max_points : 0) + 64)) != PZG_RC_OK) return rc;
+            d_in = (const uint8_t *)ln.d_in[0].p;
+            d_out = (uint8_t *)ln.d_out[0].p;
+            d_pts = (uint64_t *)(d_out + pts_off);
+            d_win = windows ? d_out + win_off : nullptr;
+            if (in_len) HIP_TRY(ctx, hipMemcpyAsync(ln.d_in[0].p, in, in_len, hipMemcpyHostToDevice, st));
+        }
+        if ((rc = arena_reserve(ctx, ln.d_meta[0], 256)) != PZG_RC_OK) return rc;
+        uint8_t *dm = (uint8_t *)ln.d_meta[0].p;
+        // [0] in_off [1] in_len [2] out_off [3] out_cap | [4] out_len [5] in_used | words: status, adler, detail0, detail1, points
+        uint64_t hm[8] = {0, in_len, 0, out_cap, 0, 0, 0, 0};
+        HIP_TRY(ctx, hipMemcpyAsync(dm, hm, sizeof(hm), hipMemcpyHostToDevice, st));
+        pzg::InflateArgs a{};
+        a.in_base = d_in;
+        a.out_base = d_out;
+        a.in_off = (const uint64_t *)dm;
+        a.in_len = a.in_off + 1;
+        a.out_off = a.in_off + 2;
+        a.out_cap = a.in_off + 3;
+        a.out_len = (uint64_t *)dm + 4;
+        a.in_used = (uint64_t *)dm + 5;
+        a.status = (int32_t *)(dm + 48);
+        a.adler = (uint32_t *)(dm + 52);
+        a.detail = (uint32_t *)(dm + 56);
+        a.n = 1;
+        a.counter = ln.d_counter;
+        a.raw = 1u;
+        a.seg = 1u;
+        a.idx_points = d_pts;
+        a.idx_count = (uint32_t *)(dm + 64);
+        a.idx_span = span;
+        a.idx_cap = max_points;
+        if (!d_pts) {  // (max_points = 0: the points are counted all the same; the kernel stores none)
+            a.idx_points = (uint64_t *)(dm + 128);
+            a.idx_cap = 0;
+        }
+        HIP_TRY(ctx, hipEventRecord(ln.ev_t0, st));
+        HIP_TRY(ctx, pzg::launch_inflate(a, 15, sh.num_cus, st));
+        HIP_TRY(ctx, pzg::launch_index_windows(d_out, a.out_cap, a.idx_points, a.idx_count, a.idx_cap, a.status, d_win, st));
+        HIP_TRY(ctx, hipEventRecord(ln.ev_t1, st));
+        HIP_TRY(ctx, hipMemcpyAsync(hm, dm, sizeof(hm), hipMemcpyDeviceToHost, st));
+        uint32_t cnt = 0;
+        HIP_TRY(ctx, hipMemcpyAsync(&cnt, dm + 64, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        uint32_t w[4];
+        memcpy(w, &hm[6], 16);
+        *out_len = hm[4];
+        *status = (int32_t)w[0];
+        if (in_used) *in_used = hm[5];
+        if (adler) *adler = w[1];
+        if (detail) {
+            detail[0] = w[2];
+            detail[1] = w[3];
+        }
+        *npoints = cnt;
+        if (!dev) {
+            const uint64_t nb = hm[4] < out_cap ? hm[4] : out_cap;
+            const size_t np = cnt < max_points ? cnt : max_points;
+            if (nb) HIP_TRY(ctx, hipMemcpy(out, d_out, nb, hipMemcpyDeviceToHost));
+            if (np) HIP_TRY(ctx, hipMemcpy(points, d_pts, 16 * np, hipMemcpyDeviceToHost));
+            if (np && windows && w[0] == 0u) {
+                // (a point below 32768 has a shorter window, at the end of its slot: the front of the caller's slot stays as it is.
+                // out_pos ascends, so these are the first few points; whole slots follow in one copy)
+                size_t k = 0;
+                for (; k < np && points[k].out_pos < 32768u; ++k) {
+                    const size_t at = 32768u * k + (32768u - (size_t)points[k].out_pos);
+                    HIP_TRY(ctx, hipMemcpy(windows + at, d_win + at, (size_t)points[k].out_pos, hipMemcpyDeviceToHost));
+                }
+                if (k < np) HIP_TRY(ctx, hipMemcpy(windows + 32768u * k, d_win + 32768u * k, 32768u * (np - k), hipMemcpyDeviceToHost));
+            }
+        }
+        {
+            float ms = -1.0f;
+            const bool ok = hipEventElapsedTime(&ms, ln.ev_t0, ln.ev_t1) == hipSuccess;
+            std::lock_guard<std::mutex> g(sh.mu);
+            sh.host_ms = ok ? (double)ms : -1.0;
+            sh.last_was_host = true;
+            sh.timed = true;
+        }
+        return PZG_RC_OK;
+    } catch (const std::bad_alloc &) {
+        return PZG_RC_NO_MEMORY;
     }
 }
 
@@ -2000,6 +2185,7 @@ const char *pzg_strerror(int rc)
     case PZG_RC_NO_DEVICE: return "no usable HIP device (this library has no CPU fallback)";
     case PZG_RC_HIP_ERROR: return "HIP runtime error";
     case PZG_RC_NO_MEMORY: return "out of memory";
+    case PZG_E_SEGMENT: return "Format error: segment does not end on its block boundary";  // (a per-stream status, for callers that pass one)
     default: return "unknown return code";
     }
 }

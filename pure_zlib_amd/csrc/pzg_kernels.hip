@@ -247,7 +247,9 @@ hipError_t launch_inflate(const InflateArgs &a_in, int ring_bits, int num_cus, h
         else                                                                                  \
             hipLaunchKernelGGL((inflate_kernel<RB, false, false>), grid, block, 0, stream, a); \
     } while (0)
-    if (ring_bits == 15)
+    if (a.seg)  // segments of an indexed stream: their history is a dictionary, which only the 32 KiB ring holds -- no small-ring launch
+        e = launch_inflate_seg(a, launch_waves(15, num_cus, a.n, 0u), stream);
+    else if (ring_bits == 15)
         PZG_LAUNCH_RING(15);
     else if (ring_bits == 14)
         PZG_LAUNCH_RING(14);
@@ -263,7 +265,7 @@ hipError_t launch_inflate(const InflateArgs &a_in, int ring_bits, int num_cus, h
     if (e != hipSuccess) return e;
     e = hipGetLastError();
     if (e != hipSuccess) return e;
-    if (ring_bits != 15) {
+    if (ring_bits != 15 && !a.seg) {
         // streams whose output outgrew their capacity are redone by the pure-LDS-ring kernel
         e = hipMemsetAsync(a.counter, 0, sizeof(uint32_t), stream);
         if (e != hipSuccess) return e;

@@ -2,6 +2,8 @@
 //
 //   inflate_resume_kernel           the resumable decoder (decompressIncremental)
 //   inflate_kernel<RB, *, true>     the gzip instances
+//   inflate_raw_kernel<RB, *>       the raw instances
+//   inflate_seg_kernel              the segment instance (indexed streams), and index_windows_kernel beside it
 //
 // SDWA forms save a vector instruction here and there (an extract folded into an add) but take their operands from registers
 // only: with the peephole on, a dozen small constants live in vector registers from the kernel's first line to its last.  The
@@ -50,6 +52,104 @@ hipError_t launch_inflate_raw(const InflateArgs &a, int ring_bits, bool fixup, u
         hipLaunchKernelGGL((inflate_raw_kernel<11, false>), grid, block, 0, stream, a);
     else
         return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// Indexed streams (pzg_index_build / pzg_decompress_many_segments).  The segment instance: the raw kernel's persistent stream-waves
+// around Decoder<15, false, false, true, true> -- a segment starts at a bit inside its first byte, ends with the block that ends at its
+// end bit, and has the 32 KiB in front of it as its dictionary; the index build is ONE such "segment", the whole stream, that records
+// the access points as it goes.  The 32 KiB ring only (a dictionary is history on that ring alone), without the token scratch, as
+// the fixup pass.
+__global__ __launch_bounds__(64, waves_per_simd(15)) void inflate_seg_kernel(InflateArgs)
+{
+    typedef Decoder<15, false, false, true, true> SegDecoder;
+    __shared__ WaveLds<15> lds;
+    if (threadIdx.x == 0) lds.fixed_ready = 0u;  // LDS is not zeroed at launch
+    __syncthreads();
+    for (;;) {
+        uint32_t i = 0, npoints = 0;
+        StreamResult r;
+        {
+            LaunchArgs a = launch_args();
+            if (threadIdx.x == 0) i = atomicAdd(a->counter, 1u);
+            i = uni(i);
+            if (i >= a->n) break;
+            if (a->order) i = a->order[i];
+            SegDecoder dec(lds);
+            uint32_t *none = nullptr;  // (made opaque: see inflate_raw_kernel)
+            asm volatile("" : "+s"(none));
+            dec.strip = none;
+            const uint8_t *dict = nullptr;
+            uint32_t dict_len = 0;
+            if (a->dict_len) {
+                const uint64_t dl = a->dict_len[i];
+                dict = a->dict_base + a->dict_off[i];
+                dict_len = uni(dl > 0xffffffffull ? 0xffffffffu : (uint32_t)dl);
+            }
+            dec.seg_start = a->seg_start_bit ? uni((uint32_t)a->seg_start_bit[i]) : 0u;
+            dec.seg_end = a->seg_end_bit ? uni64(a->seg_end_bit[i]) : 0ull;
+            dec.idx_points = (IndexPoint *)(void *)a->idx_points;
+            dec.idx_cap = a->idx_cap;
+            dec.idx_span = a->idx_points ? a->idx_span : 0ull;
+            dec.run(a->in_base + a->in_off[i], a->in_len[i], a->out_base + a->out_off[i], a->out_cap[i], &r, dict, dict_len);
+            npoints = dec.idx_n;
+        }
+        LaunchArgs a = launch_args();
+        if (threadIdx.x == 0) {
+            a->status[i] = r.status;
+            a->out_len[i] = r.out_len;
+            if (a->detail) {
+                a->detail[2 * (size_t)i] = r.detail0;
+                a->detail[2 * (size_t)i + 1] = r.detail1;
+            }
+            if (a->in_used) a->in_used[i] = r.in_used;
+            if (a->adler) a->adler[i] = r.adler;  // (PZG_CRC32: crc32_report_kernel then writes the CRC-32 over it)
+            if (a->idx_count) *a->idx_count = npoints;
+        }
+        __syncthreads();
+    }
+}
+
+hipError_t launch_inflate_seg(const InflateArgs &a, uint32_t waves, hipStream_t stream)
+{
+    hipLaunchKernelGGL(inflate_seg_kernel, dim3(waves), dim3(64), 0, stream, a);
+    return hipGetLastError();
+}
+
+// One workgroup per stored point (grid-stride): w = min(out_pos, 32768) bytes out[out_pos - w .. out_pos) to the end of the point's slot.
+// Bytes up to the first 16-byte boundary of the destination, then a vector per lane (the source is wherever it is), then a byte tail.
+__global__ __launch_bounds__(256) void index_windows_kernel(const uint8_t *out, const uint64_t *out_cap, const uint64_t *points, const uint32_t *count,
+                                                            uint32_t cap, const int32_t *status, uint8_t *windows)
+{
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    if (*status != ST_OK) return;
+    const uint32_t n = *count < cap ? *count : cap;
+    const uint64_t room = *out_cap;
+    for (uint32_t k = blockIdx.x; k < n; k += gridDim.x) {
+        const uint64_t pos = points[2 * (size_t)k + 1];
+        if (pos > room) continue;  // (never with status 0: nothing outside the output is ever read)
+        const uint32_t w = pos < 32768u ? (uint32_t)pos : 32768u;
+        const uint8_t *src = out + (pos - w);
+        uint8_t *dst = windows + (size_t)k * 32768u + (32768u - w);
+        uint32_t head = (16u - (uint32_t)((uintptr_t)dst & 15u)) & 15u;
+        head = head < w ? head : w;
+        const uint32_t nv = (w - head) >> 4;
+        for (uint32_t t = threadIdx.x; t < head; t += blockDim.x) dst[t] = src[t];
+        for (uint32_t v = threadIdx.x; v < nv; v += blockDim.x) {
+            u32x4 x;
+            __builtin_memcpy(&x, src + head + 16u * v, 16);
+            *(u32x4 *)(void *)(dst + head + 16u * v) = x;
+        }
+        for (uint32_t t = head + 16u * nv + threadIdx.x; t < w; t += blockDim.x) dst[t] = src[t];
+    }
+}
+
+hipError_t launch_index_windows(const uint8_t *out, const uint64_t *out_cap, const uint64_t *points, const uint32_t *count, uint32_t cap,
+                                const int32_t *status, uint8_t *windows, hipStream_t stream)
+{
+    if (cap == 0u || !windows) return hipSuccess;
+    hipLaunchKernelGGL(index_windows_kernel, dim3(cap < 4096u ? cap : 4096u), dim3(256), 0, stream, out, out_cap, points, count, cap, status, windows);
     return hipGetLastError();
 }
 

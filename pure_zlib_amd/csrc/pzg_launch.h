@@ -38,6 +38,18 @@ struct InflateArgs {
     // extension (PZG_RAW): 1 -- bare RFC 1951 streams, no header, no trailer, nothing checked (dictionaries apply unconditionally);
     // 2 -- and adler[] gets the CRC-32 of the bytes delivered instead of their Adler-32 (PZG_CRC32: one more pass over the output)
     uint32_t raw;
+    // extension (indexed streams; raw != 0): nonzero -- the streams are SEGMENTS of a raw stream (pzg_kernels_b.hip inflate_seg_kernel, the
+    // 32 KiB ring whatever the launch's ring): stream i starts at bit seg_start_bit[i] (0..7) of its first byte and ends with the block
+    // that ends at bit seg_end_bit[i], counted from that byte's bit 0 (0: with the final block); either array may be null (all zeros)
+    uint32_t seg;
+    const uint8_t *seg_start_bit;  // n or null
+    const uint64_t *seg_end_bit;   // n or null
+    // ... and, idx_span != 0 (n = 1: the index build), the access points of the stream: {in_bit, out_pos} pairs, the first idx_cap of
+    // them stored, all of them counted in *idx_count
+    uint64_t *idx_points;
+    uint32_t *idx_count;
+    uint64_t idx_span;
+    uint32_t idx_cap;
 };
 
 // one batched call of the resumable decoder (decompressIncremental): decoder i continues from its ResumeState
@@ -86,6 +98,14 @@ hipError_t launch_profile_switch(uint32_t *strip, uint32_t waves, bool off, hipS
 hipError_t launch_inflate_gzip(const InflateArgs &a, int ring_bits, bool fixup, uint32_t waves, hipStream_t stream);
 // the raw instances: the same
 hipError_t launch_inflate_raw(const InflateArgs &a, int ring_bits, bool fixup, uint32_t waves, hipStream_t stream);
+
+// the segment instance (pzg_kernels_b.hip): `waves` workgroups of the 32 KiB ring's kernel
+hipError_t launch_inflate_seg(const InflateArgs &a, uint32_t waves, hipStream_t stream);
+// the 32 KiB of output in front of every stored point of an index build, min(*count, cap) of them, into the END of slot k of `windows`
+// (cap x 32768 bytes; a point below 32768 has that much less, the front of its slot is left as it is).  Nothing is copied unless
+// *status is 0 and the point lies inside out_cap.
+hipError_t launch_index_windows(const uint8_t *out, const uint64_t *out_cap, const uint64_t *points, const uint32_t *count, uint32_t cap,
+                                const int32_t *status, uint8_t *windows, hipStream_t stream);
 
 // partials: 3 * 4 * ceil(max_waves / 4) uint32 of device scratch
 hipError_t launch_adler32(const uint8_t *buf, uint64_t len, uint32_t init, uint32_t *partials, uint32_t max_waves,

@@ -10,6 +10,11 @@ deflate --many a.z b.z c.z ...  decodes every file in ONE `decompressMany` call 
 ByteString `L.readFile` would make of it, so `decompress`'s own outcomes apply per file: "ERROR: <show e>" for a Left
 (including Zlib.hs:48-49's "Finished with data remaining."), "Unexpected file name." for a name that does not end in
 ".z"; the other files are still decoded.
+
+Indexed mode (on top of the reference too; pure_zlib_amd/indexed.py), for ONE large file -- foo.z (zlib) or foo.gz (gzip, one member):
+deflate --index foo.pzi foo.z                          one sequential pass: writes foo and the index of access points foo.pzi
+deflate --use-index foo.pzi [--range OFF:LEN] foo.z    decodes foo with a wavefront per segment of the index and writes it; with
+                                                       --range only the segments that cover LEN bytes from OFF, written to stdout
 """
 import sys
 
@@ -63,10 +68,61 @@ def run_many(files) -> None:
             print(f"{f}: ERROR: " + r.value.show())
 
 
+def _kind_and_target(name):
+    for ext, kind in ((".z", "zlib"), (".gz", "gzip")):
+        if name.endswith(ext):
+            return kind, name[:-len(ext)]
+    return None, None
+
+
+def run_indexed(args) -> None:
+    """Indexed mode: --index FILE.pzi NAME | --use-index FILE.pzi [--range OFF:LEN] NAME."""
+    from .indexed import Index
+    from .zlib import DecompressionError
+    build = args[0] == "--index"
+    rng = None
+    rest = args[2:]
+    if not build and len(rest) >= 2 and rest[0] == "--range":
+        try:
+            rng = tuple(int(x) for x in rest[1].split(":"))
+        except ValueError:
+            rng = ()
+        rest = rest[2:]
+    if len(args) < 2 or len(rest) != 1 or (rng is not None and (len(rng) != 2 or min(rng) < 0)):
+        print("USAGE: deflate --index FILE.pzi filename | deflate --use-index FILE.pzi [--range OFF:LEN] filename")
+        return
+    kind, target = _kind_and_target(rest[0])
+    if kind is None:
+        print("Unexpected file name.")
+        return
+    with open(rest[0], "rb") as f:
+        data = f.read()
+    if build:
+        index, r = Index.build(data, kind)
+        if index is not None:
+            index.save(args[1])
+    elif rng is not None:
+        try:
+            sys.stdout.buffer.write(Index.load(args[1]).read(data, rng[0], rng[1]))
+        except DecompressionError as e:
+            print("ERROR: " + e.show())
+        return
+    else:
+        r = Index.load(args[1]).decompress(data)
+    if r.is_right():
+        with open(target, "wb") as out:
+            out.write(r.value)
+    else:
+        print("ERROR: " + r.value.show())
+
+
 def main(argv=None) -> int:
     args = sys.argv[1:] if argv is None else argv
     if args and args[0] == "--many":
         run_many(args[1:])
+        return 0
+    if args and args[0] in ("--index", "--use-index"):
+        run_indexed(args)
         return 0
     if len(args) != 1:  # Deflate.hs:17-29
         print("USAGE: deflate [filename]")
