@@ -90,6 +90,10 @@ extern "C" {
 #define PZG_E_DICT               20  /* "Header error: preset dictionary mismatch: <hex d0> != <hex d1>": the stream's DICTID (d0) is
                                       * not the Adler-32 of the dictionary supplied for it (d1) */
 #define PZG_E_SEGMENT 21  /* segments only: the blocks do not end at end_bit. d0 = 1 final block came first, 2 a block ran past; d1 = bit reached */
+#define PZG_E_SCAN 22  /* pzg_index_scan only: the chain of blocks did not reach the final block.
+                          d0 = the status the chain's last segment met (0: a dead wave),
+                          d1 = low 32 bits of that segment's start bit.
+                          Decode sequentially for the stream's own error. */
 /* Reference raise sites that have NO status because they cannot fire (here or in the reference):
  *   Deflate.hs:150-151  DecompressionError "Unexpected code: <n>" -- getCodeLengths' fall-through for a code-length symbol outside
  *                       0..18; the code-length alphabet has exactly 19 symbols (Deflate.hs:87-88 builds its tree from 19 lengths),
@@ -345,6 +349,41 @@ PZG_API int pzg_index_build(pzg_ctx *ctx, const uint8_t *in, uint64_t in_len,
         uint8_t *windows,                                       /* max_points x 32768 bytes, or NULL */
         uint64_t *out_len, int32_t *status, uint32_t detail[2], uint64_t *in_used, uint32_t *adler,
         uint32_t flags);                                        /* PZG_DEVICE_PTRS or 0; PZG_RAW implied */
+
+/*
+ * pzg_index_scan: the access points of ONE raw (RFC 1951) stream found IN PARALLEL, without the sequential decode of pzg_index_build
+ * (the block finder plus marker window scheme of pugz and rapidgzip).  The input is cut into chunks of `chunk` compressed bytes;
+ *   1. a wavefront per chunk k >= 1 finds the smallest bit position of its chunk at which a CANDIDATE block header starts (chunk 0
+ *      starts at bit 0, a block start by definition).  A candidate, exactly: BFINAL = 0 and BTYPE = 2; HLIT <= 29 and HDIST <= 29; the
+ *      HCLEN + 4 lengths of the code-length code form a complete prefix code (Kraft sum exactly 1); the run-length expansion yields
+ *      exactly HLIT + 257 + HDIST + 1 lengths, with no repeat-previous (16) at position 0 and no run crossing the end; symbol 256 has a
+ *      nonzero length; the literal/length code is complete; the distance code is complete, or has exactly one code of length 1, or
+ *      has no codes at all; the whole header lies inside the input.  Fixed and stored blocks are not looked for: a stream made only
+ *      of those has no candidates and is one segment (a limit, not an error);
+ *   2. a wavefront per candidate decodes from there with the 32 KiB in front of it as MARKERS instead of bytes, until a block ends
+ *      exactly at a later candidate, or the final block ends, or an error (a wave that passes 8 candidates without landing on one is
+ *      given up as started at a false candidate);
+ *   3. one workgroup walks the chain of segments from bit 0, resolves each segment's last 32 KiB against the window in front of it,
+ *      and applies pzg_index_build's rule: a link of the chain is a point when its out_pos is `span` or more past the last point's.
+ * points, max_points, npoints (the count the stream HAS at this span and chunk: more than max_points means only the first max_points
+ * were stored), windows (the window at the END of its slot), in_used, the host / device pointer forms (npoints, out_len, status,
+ * detail and in_used are host memory in both), the one-device context, the rejected flags and the stream of the library's own are
+ * those of pzg_index_build.  No output bytes and no checksum are produced: *out_len is the decoded size.  The points are a subset of
+ * the stream's block boundaries, in general not the ones pzg_index_build picks; nothing but the segments' decode
+ * (pzg_decompress_many_segments) and the checksum over it proves them, so verify before trusting them (the Python mirror's
+ * Index.build_parallel does).
+ *   *status   PZG_OK, or PZG_E_SCAN: the chain ended in an error or in a dead wave (a broken stream; or, in principle, eight false
+ *             candidates in a row).  pzg_index_build or pzg_decompress_many then gives the stream's own error.
+ *   chunk     compressed bytes per chunk; 0: 128 KiB; below 256: PZG_RC_BAD_ARG.  span 0: 1 MiB.
+ * Device memory: 64 KiB + 32 bytes per chunk (in_len / chunk of them) plus 64.25 KiB, allocated for the call and freed before it
+ * returns -- 2,048 chunks of 128 KiB, a 256 MiB input: 128 MiB; PZG_RC_NO_MEMORY when the device does not have it.
+ */
+PZG_API int pzg_index_scan(pzg_ctx *ctx, const uint8_t *in, uint64_t in_len,
+        uint64_t chunk,   /* compressed bytes per chunk; 0: 128 KiB; below 256: PZG_RC_BAD_ARG */
+        uint64_t span,    /* 0: 1 MiB */
+        pzg_index_point *points, uint32_t max_points, uint32_t *npoints, uint8_t *windows,
+        uint64_t *out_len, int32_t *status, uint32_t detail[2], uint64_t *in_used,
+        uint32_t flags);  /* 0 or PZG_DEVICE_PTRS */
 
 PZG_API int pzg_decompress_many_segments(pzg_ctx *ctx,
         const uint8_t *in_base, const uint64_t *in_off, const uint64_t *in_len,

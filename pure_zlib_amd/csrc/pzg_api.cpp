@@ -1455,6 +1455,108 @@ int pzg_index_build(pzg_ctx *ctx, const uint8_t *in, uint64_t in_len, uint8_t *o
     }
 }
 
+int pzg_index_scan(pzg_ctx *ctx, const uint8_t *in, uint64_t in_len, uint64_t chunk, uint64_t span, pzg_index_point *points, uint32_t max_points,
+                   uint32_t *npoints, uint8_t *windows, uint64_t *out_len, int32_t *status, uint32_t detail[2], uint64_t *in_used, uint32_t flags)
+{
+    if (!ctx_live(ctx)) return PZG_RC_BAD_ARG;
+    if (flags & ~(PZG_DEVICE_PTRS | PZG_RAW)) return PZG_RC_BAD_ARG;  // (PZG_RAW is implied, as for pzg_index_build)
+    if (ctx->shards.size() != 1) return PZG_RC_BAD_ARG;
+    if (!in || !npoints || !out_len || !status || (max_points && !points)) return PZG_RC_BAD_ARG;
+    if (in_len >> 34) return PZG_RC_BAD_ARG;
+    if (chunk == 0) chunk = 128u << 10;
+    if (chunk < 256u) return PZG_RC_BAD_ARG;
+    if (span == 0) span = 1ull << 20;
+    const uint64_t nchunks64 = in_len ? (in_len + chunk - 1u) / chunk : 1u;
+    const bool dev = (flags & PZG_DEVICE_PTRS) != 0;
+    Shard &sh = *ctx->shards[0];
+    Lane &ln = sh.lanes[0];
+    // the call's own scratch, freed whatever way the call ends
+    struct Scratch {
+        void *p = nullptr;
+        ~Scratch()
+        {
+            if (p) (void)hipFree(p);
+        }
+    } scratch;
+    try {
+        std::lock_guard<std::mutex> lk(ln.mu);
+        HIP_TRY(ctx, hipSetDevice(sh.device));
+        int rc = lane_prepare(ctx, ln);
+        if (rc != PZG_RC_OK) return rc;
+        hipStream_t st = ln.s_k;
+        const uint8_t *d_in = in;
+        uint8_t *d_win = windows;
+        uint64_t *d_pts = (uint64_t *)points;
+        const size_t win_off = pad256(16 * (size_t)max_points);
+        if (!dev) {
+            if ((rc = arena_reserve(ctx, ln.d_in[0], in_len + 64)) != PZG_RC_OK) return rc;
+            if ((rc = arena_reserve(ctx, ln.d_out[0], win_off + (windows ? 32768 * (size_t)max_points : 0) + 64)) != PZG_RC_OK) return rc;
+            d_in = (const uint8_t *)ln.d_in[0].p;
+            d_pts = (uint64_t *)ln.d_out[0].p;
+            d_win = windows ? (uint8_t *)ln.d_out[0].p + win_off : nullptr;
+            if (in_len) HIP_TRY(ctx, hipMemcpyAsync(ln.d_in[0].p, in, in_len, hipMemcpyHostToDevice, st));
+        }
+        if ((rc = arena_reserve(ctx, ln.d_meta[0], 256)) != PZG_RC_OK) return rc;
+        const size_t need = pzg::scan_scratch_bytes((uint32_t)nchunks64);
+        if (hipMalloc(&scratch.p, need) != hipSuccess) {
+            (void)hipGetLastError();
+            scratch.p = nullptr;
+            return PZG_RC_NO_MEMORY;
+        }
+        pzg::ScanArgs a{};
+        a.in = d_in;
+        a.in_len = in_len;
+        a.chunk = chunk;
+        a.span = span;
+        a.nchunks = (uint32_t)nchunks64;
+        a.max_points = d_pts ? max_points : 0u;
+        a.points = d_pts;
+        a.windows = d_win;
+        a.result = (pzg::ScanResult *)ln.d_meta[0].p;
+        HIP_TRY(ctx, hipEventRecord(ln.ev_t0, st));
+        HIP_TRY(ctx, pzg::launch_scan(a, (uint8_t *)scratch.p, st));
+        HIP_TRY(ctx, hipEventRecord(ln.ev_t1, st));
+        struct {
+            int32_t status;
+            uint32_t d0, d1, npoints;
+            uint64_t out_len, in_used;
+        } r{};
+        HIP_TRY(ctx, hipMemcpyAsync(&r, ln.d_meta[0].p, sizeof(r), hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        *out_len = r.out_len;
+        *status = r.status;
+        if (in_used) *in_used = r.in_used;
+        if (detail) {
+            detail[0] = r.d0;
+            detail[1] = r.d1;
+        }
+        *npoints = r.npoints;
+        if (!dev && r.status == 0) {
+            const size_t np = r.npoints < max_points ? r.npoints : max_points;
+            if (np) HIP_TRY(ctx, hipMemcpy(points, d_pts, 16 * np, hipMemcpyDeviceToHost));
+            if (np && windows) {  // (as pzg_index_build: the front of a short window's slot stays the caller's)
+                size_t k = 0;
+                for (; k < np && points[k].out_pos < 32768u; ++k) {
+                    const size_t at = 32768u * k + (32768u - (size_t)points[k].out_pos);
+                    HIP_TRY(ctx, hipMemcpy(windows + at, d_win + at, (size_t)points[k].out_pos, hipMemcpyDeviceToHost));
+                }
+                if (k < np) HIP_TRY(ctx, hipMemcpy(windows + 32768u * k, d_win + 32768u * k, 32768u * (np - k), hipMemcpyDeviceToHost));
+            }
+        }
+        {
+            float ms = -1.0f;
+            const bool ok = hipEventElapsedTime(&ms, ln.ev_t0, ln.ev_t1) == hipSuccess;
+            std::lock_guard<std::mutex> g(sh.mu);
+            sh.host_ms = ok ? (double)ms : -1.0;
+            sh.last_was_host = true;
+            sh.timed = true;
+        }
+        return PZG_RC_OK;
+    } catch (const std::bad_alloc &) {
+        return PZG_RC_NO_MEMORY;
+    }
+}
+
 int pzg_decompress_many_sharded(pzg_ctx *ctx, const pzg_device_batch *batches, uint32_t nbatches, uint32_t flags)
 {
     if (!ctx_live(ctx) || (!batches && nbatches)) return PZG_RC_BAD_ARG;

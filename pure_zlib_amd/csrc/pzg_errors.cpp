@@ -196,6 +196,7 @@ extern "C" int pzg_error_message(const uint8_t *in, uint64_t in_len, int32_t sta
     case PZG_E_GZIP_ISIZE: snprintf(buf, buf_len, "Checksum error: gzip: length mismatch: %u != %u", d0, d1); break;
     case PZG_E_DICT: snprintf(buf, buf_len, "Header error: preset dictionary mismatch: %x != %x", d0, d1); break;  // extension
     case PZG_E_SEGMENT: snprintf(buf, buf_len, "Format error: segment does not end on its block boundary"); break;  // extension
+    case PZG_E_SCAN: snprintf(buf, buf_len, "Format error: the chain of blocks did not reach the final block"); break;  // extension
     default: snprintf(buf, buf_len, "unknown status %d", status); break;
     }
     return (int)strlen(buf);

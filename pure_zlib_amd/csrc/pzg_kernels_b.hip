@@ -4,6 +4,7 @@
 //   inflate_kernel<RB, *, true>     the gzip instances
 //   inflate_raw_kernel<RB, *>       the raw instances
 //   inflate_seg_kernel              the segment instance (indexed streams), and index_windows_kernel beside it
+//   scan_find / scan_decode / scan_resolve_kernel   the parallel index scan (scan_core.h)
 //
 // SDWA forms save a vector instruction here and there (an extract folded into an add) but take their operands from registers
 // only: with the peephole on, a dozen small constants live in vector registers from the kernel's first line to its last.  The
@@ -11,6 +12,7 @@
 // have more state: without it the resumable kernel needs no scratch memory (12 spilled vector registers with it) and runs
 // 27 % faster (31.1 vs 24.4 GiB/s, bench.py's incremental leg), and the ring-11 gzip instance fits 72 registers (80 and one spill).
 #include "pzg_inflate_kernel.h"
+#include "scan_core.h"
 
 namespace pzg {
 
@@ -150,6 +152,79 @@ hipError_t launch_index_windows(const uint8_t *out, const uint64_t *out_cap, con
 {
     if (cap == 0u || !windows) return hipSuccess;
     hipLaunchKernelGGL(index_windows_kernel, dim3(cap < 4096u ? cap : 4096u), dim3(256), 0, stream, out, out_cap, points, count, cap, status, windows);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// The parallel index scan (pzg_index_scan; scan_core.h): a wave per chunk finds a candidate block start, a wave per candidate decodes
+// over markers until it lands on a later candidate, one workgroup walks the chain and writes the points and their windows.
+__device__ __forceinline__ void scan_input(const ScanArgs &a, const uint32_t *&src, uint64_t &ndw, uint32_t &mis_bits, uint64_t &end_bit)
+{
+    const uint32_t mis = (uint32_t)((uintptr_t)a.in & 3u);
+    src = (const uint32_t *)(const void *)(a.in - mis);
+    ndw = (mis + a.in_len + 3u) >> 2;
+    mis_bits = 8u * mis;
+    end_bit = 8u * (mis + a.in_len);
+}
+
+__global__ __launch_bounds__(64) void scan_find_kernel(ScanArgs a)
+{
+    __shared__ ScanLds lds;
+    const uint32_t k = blockIdx.x;
+    if (k >= a.nchunks) return;
+    uint64_t q = 0;
+    if (k) {
+        const uint32_t *src;
+        uint64_t ndw, end_bit;
+        uint32_t mis_bits;
+        scan_input(a, src, ndw, mis_bits, end_bit);
+        const uint64_t from = 8u * k * a.chunk, all = 8u * a.in_len;
+        const uint64_t to = from + 8u * a.chunk < all ? from + 8u * a.chunk : all;
+        q = Scan::find(lds, src, ndw, end_bit, from + mis_bits, to + mis_bits);
+        if (q != Scan::NONE) q -= mis_bits;
+    }
+    if (threadIdx.x == 0) a.cand[k] = q;
+}
+
+__global__ __launch_bounds__(64) void scan_decode_kernel(ScanArgs a)
+{
+    __shared__ ScanLds lds;
+    const uint32_t k = blockIdx.x;
+    if (k >= a.nchunks) return;
+    const uint32_t *src;
+    uint64_t ndw, end_bit;
+    uint32_t mis_bits;
+    scan_input(a, src, ndw, mis_bits, end_bit);
+    Scan::decode(lds, src, ndw, mis_bits, end_bit, a.cand, a.nchunks, k, a.rings + (size_t)k * Scan::RING, a.next, a.count, a.endbit);
+}
+
+__global__ __launch_bounds__(1024) void scan_resolve_kernel(ScanArgs a)
+{
+    Scan::resolve(threadIdx.x, blockDim.x, a.cand, a.next, a.count, a.endbit, a.rings, a.nchunks, a.span, a.wbuf, a.points, a.max_points,
+                  a.windows, a.result);
+}
+
+size_t scan_scratch_bytes(uint32_t nchunks)
+{
+    // per chunk: the ring (64 KiB) and 32 bytes -- cand, count, endbit (8 each), next (4), 4 to spare; the chain walk's two windows
+    // (64 KiB) and 256 bytes of slack: the figure include/pzg.h documents
+    return (size_t)nchunks * (2u * Scan::RING + 32u) + 2u * Scan::RING + 256u;
+}
+
+hipError_t launch_scan(ScanArgs a, uint8_t *scratch, hipStream_t stream)
+{
+    const size_t n = a.nchunks;
+    a.rings = (uint16_t *)(void *)scratch;
+    uint8_t *p = scratch + n * 2u * Scan::RING;
+    a.wbuf = p;
+    p += 2u * Scan::RING;
+    a.cand = (uint64_t *)(void *)p;
+    a.count = a.cand + n;
+    a.endbit = a.count + n;
+    a.next = (uint32_t *)(void *)(a.endbit + n);
+    hipLaunchKernelGGL(scan_find_kernel, dim3(a.nchunks), dim3(64), 0, stream, a);
+    hipLaunchKernelGGL(scan_decode_kernel, dim3(a.nchunks), dim3(64), 0, stream, a);
+    hipLaunchKernelGGL(scan_resolve_kernel, dim3(1), dim3(1024), 0, stream, a);
     return hipGetLastError();
 }
 

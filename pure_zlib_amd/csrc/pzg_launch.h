@@ -107,6 +107,25 @@ hipError_t launch_inflate_seg(const InflateArgs &a, uint32_t waves, hipStream_t 
 hipError_t launch_index_windows(const uint8_t *out, const uint64_t *out_cap, const uint64_t *points, const uint32_t *count, uint32_t cap,
                                 const int32_t *status, uint8_t *windows, hipStream_t stream);
 
+// the parallel index scan (pzg_kernels_b.hip, scan_core.h).  The caller fills in what is above the line; launch_scan() lays the rest
+// out in `scratch` (scan_scratch_bytes(nchunks) bytes of device memory, 256-byte aligned) and enqueues the three kernels.
+struct ScanResult;
+struct ScanArgs {
+    const uint8_t *in;
+    uint64_t in_len, chunk, span;
+    uint32_t nchunks, max_points;
+    uint64_t *points;    // max_points {in_bit, out_pos} pairs
+    uint8_t *windows;    // max_points x 32768 bytes, or null
+    ScanResult *result;  // 32 bytes: status, d0, d1, npoints, out_len, in_used
+    // ----
+    uint64_t *cand, *count, *endbit;
+    uint32_t *next;
+    uint16_t *rings;
+    uint8_t *wbuf;
+};
+size_t scan_scratch_bytes(uint32_t nchunks);
+hipError_t launch_scan(ScanArgs a, uint8_t *scratch, hipStream_t stream);
+
 // partials: 3 * 4 * ceil(max_waves / 4) uint32 of device scratch
 hipError_t launch_adler32(const uint8_t *buf, uint64_t len, uint32_t init, uint32_t *partials, uint32_t max_waves,
                           uint32_t *out, hipStream_t stream);

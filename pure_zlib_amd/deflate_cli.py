@@ -13,6 +13,8 @@ ByteString `L.readFile` would make of it, so `decompress`'s own outcomes apply p
 
 Indexed mode (on top of the reference too; pure_zlib_amd/indexed.py), for ONE large file -- foo.z (zlib) or foo.gz (gzip, one member):
 deflate --index foo.pzi foo.z                          one sequential pass: writes foo and the index of access points foo.pzi
+deflate --index foo.pzi --parallel foo.z               the same without the sequential pass: the access points are found in parallel
+                                                       (Index.build_parallel), the file is decoded by segments and verified
 deflate --use-index foo.pzi [--range OFF:LEN] foo.z    decodes foo with a wavefront per segment of the index and writes it; with
                                                        --range only the segments that cover LEN bytes from OFF, written to stdout
 """
@@ -76,12 +78,15 @@ def _kind_and_target(name):
 
 
 def run_indexed(args) -> None:
-    """Indexed mode: --index FILE.pzi NAME | --use-index FILE.pzi [--range OFF:LEN] NAME."""
+    """Indexed mode: --index FILE.pzi [--parallel] NAME | --use-index FILE.pzi [--range OFF:LEN] NAME."""
     from .indexed import Index
     from .zlib import DecompressionError
     build = args[0] == "--index"
     rng = None
     rest = args[2:]
+    parallel = build and rest[:1] == ["--parallel"]
+    if parallel:
+        rest = rest[1:]
     if not build and len(rest) >= 2 and rest[0] == "--range":
         try:
             rng = tuple(int(x) for x in rest[1].split(":"))
@@ -89,7 +94,7 @@ def run_indexed(args) -> None:
             rng = ()
         rest = rest[2:]
     if len(args) < 2 or len(rest) != 1 or (rng is not None and (len(rng) != 2 or min(rng) < 0)):
-        print("USAGE: deflate --index FILE.pzi filename | deflate --use-index FILE.pzi [--range OFF:LEN] filename")
+        print("USAGE: deflate --index FILE.pzi [--parallel] filename | deflate --use-index FILE.pzi [--range OFF:LEN] filename")
         return
     kind, target = _kind_and_target(rest[0])
     if kind is None:
@@ -98,7 +103,7 @@ def run_indexed(args) -> None:
     with open(rest[0], "rb") as f:
         data = f.read()
     if build:
-        index, r = Index.build(data, kind)
+        index, r = (Index.build_parallel if parallel else Index.build)(data, kind)
         if index is not None:
             index.save(args[1])
     elif rng is not None:

@@ -5,6 +5,7 @@ block boundary about every `span` output bytes -- its bit position, its output p
 it into segments that decode independently (pzg_decompress_many_segments):
 
     index, result = Index.build(data, kind="zlib")     # one sequential pass; result is decompress(data)'s Either
+    index, result = Index.build_parallel(data)         # the same, the points found in parallel (pzg_index_scan) and verified
     index.save("big.z.pzi"); index = Index.load("big.z.pzi")
     index.decompress(data)                             # every segment in one launch, the trailer's checksum verified
     index.read(data, offset, length)                   # only the segments that cover the range
@@ -222,6 +223,72 @@ class Index:
                 return None, Left(HeaderError("gzip: a second member follows: only a file of ONE member can be indexed"))
         index = Index(kind, span, points[:n].copy(), windows[:n].copy(), total, body_off, used, expect, _fingerprint(data, body_off + used))
         return index, Right(out[:total].tobytes())
+
+    @staticmethod
+    def build_parallel(data, kind: str = "zlib", span: int = 1 << 20, chunk: Optional[int] = None,
+                       ctx: Optional[Context] = None) -> Tuple[Optional["Index"], Either]:
+        """build() without the sequential pass: pzg_index_scan finds the access points in parallel (a wavefront per `chunk`
+        compressed bytes; None: the library's 128 KiB), then index.decompress() decodes every segment and checks the combined checksum
+        against the trailer -- that decode is what proves the points.  Returns what build() returns.  Whenever the parallel path
+        does not end in a verified success (PZG_E_SCAN, a segment's error, a checksum or length mismatch) the result is
+        Index.build(data, ...)'s: a broken stream reports the reference's own error, found by the sequential decode.  The points
+        are block boundaries about `span` apart, in general not the ones build() picks."""
+        if kind not in KINDS:
+            raise ValueError("kind must be one of %r" % (KINDS,))
+        if span < 1:
+            raise ValueError("span must be positive")
+        if chunk is not None and chunk < 256:
+            raise ValueError("chunk must be 256 or more")
+        data = bytes(data)
+        ctx = ctx or default_context()
+        sequential = lambda: Index.build(data, kind, span, ctx)
+        try:
+            body_off = 0 if kind == "raw" else parse_zlib_header(data) if kind == "zlib" else parse_gzip_header(data)
+        except DecompressionError as e:
+            return None, Left(e)
+        body = _np(data)[body_off:]
+        max_points = max(16, 4 * len(body) // span + 16)
+        L = _ffi.lib()
+        for _attempt in range(8):
+            points = np.zeros((max_points, 2), dtype=np.uint64)
+            windows = np.zeros((max_points, WINDOW), dtype=np.uint8)
+            npoints, status = C.c_uint32(0), C.c_int32(-1)
+            out_len, in_used = C.c_uint64(0), C.c_uint64(0)
+            detail = (C.c_uint32 * 2)(0, 0)
+            inp = body if len(body) else np.zeros(1, dtype=np.uint8)
+            _ffi.check(L.pzg_index_scan(ctx.handle, inp.ctypes.data, len(body), chunk or 0, span, points.ctypes.data, max_points,
+                                        C.byref(npoints), windows.ctypes.data, C.byref(out_len), C.byref(status), detail, C.byref(in_used), 0),
+                       ctx.handle)
+            if status.value != _ffi.OK:
+                return sequential()
+            if npoints.value > max_points:  # more points than room: twice the room
+                max_points = max(2 * max_points, int(npoints.value))
+                continue
+            break
+        else:
+            raise _ffi.PzgError("pzg_index_scan: no capacity settled after 8 attempts")
+        n, used, total = int(npoints.value), int(in_used.value), int(out_len.value)
+        trailer = data[body_off + used:]
+        if kind == "gzip":
+            if len(trailer) < 8 or int.from_bytes(trailer[4:8], "little") != total & 0xffffffff:
+                return sequential()
+            if trailer[8:10] == b"\x1f\x8b":
+                return None, Left(HeaderError("gzip: a second member follows: only a file of ONE member can be indexed"))
+        index = Index(kind, span, points[:n].copy(), windows[:n].copy(), total, body_off, used, 0, _fingerprint(data, body_off + used))
+        if kind == "raw":  # no trailer: the segments' combined Adler-32 stands in for it, as the build pass's does in build()
+            err, out, _base, sums, segs = index._decode(data, 0, n + 1, ctx, crc32=False)
+            if err is not None:
+                return sequential()
+            expect = 1
+            for j, s in enumerate(segs):
+                expect = adler32_combine(expect, int(sums[j]), s[5] - s[4])
+            index.expect = expect
+            return index, Right(out.tobytes())
+        r = index.decompress(data, ctx)
+        if not r.is_right():
+            return sequential()
+        index.expect = int.from_bytes(trailer[:4], "big" if kind == "zlib" else "little")
+        return index, r
 
     # -- the segments --------------------------------------------------------------------------------------------------------------
     def segments(self):
