@@ -394,6 +394,47 @@ PZG_API int pzg_decompress_many_segments(pzg_ctx *ctx,
         uint32_t n, uint32_t flags);   /* PZG_DEVICE_PTRS, PZG_ASYNC, PZG_LPT_ORDER, PZG_CRC32; PZG_RAW implied */
 
 /*
+ * EXTENSION -- a gzip FILE of many members (RFC 1952 2.2; BGZF, WARC, rotated logs, `cat a.gz b.gz`), a wavefront per member.  A
+ * member starts with an empty window, so members need no index: they are found, sized and laid out on the device, and the four
+ * arrays of pzg_gzip_layout go straight into pzg_decompress_many(..., PZG_GZIP | PZG_DEVICE_PTRS), one launch for the whole file.
+ *
+ * pzg_gzip_find_members: the input is cut into chunks of `chunk` bytes, a wavefront per chunk.  Position p is a CANDIDATE exactly
+ * when p + 10 <= in_len; the bytes at p, p + 1, p + 2 are 1f 8b 08; FLG & 0xe0 == 0; XFL is 0, 2 or 4; OS <= 13 or OS == 255.  That
+ * is stricter than the decoder's own header check on purpose: a member start the finder misses is decoded by its predecessor's
+ * wavefront, which walks on into it (slower, still correct); a candidate that is no member start (the bytes occur inside
+ * compressed data about once in 2^37 positions, and inside stored blocks whenever the data holds them) is for the caller to find by
+ * decoding: the Python mirror's decompress_gzip_file does.  Position 0 is always entry 0, whatever its bytes.
+ *   starts[]    the candidates, ascending;  bsize[]  parallel to it: 0, or -- FEXTRA set and a subfield SI1 = 66, SI2 = 67, SLEN = 2
+ *               wholly inside XLEN and inside the input -- that subfield's value plus 1, the BGZF total block size
+ *   *nmembers   the count the input HAS: if it exceeds max_members only the first max_members are stored and nothing behind them
+ *               is touched; the caller repeats with more room
+ *   chunk       bytes per chunk; 0: 64 KiB; below 64: PZG_RC_BAD_ARG.  The result does not depend on it, and is the same from run to run.
+ * pzg_gzip_layout: for the m accepted starts (ascending), member j is in_off[j] = starts[j], in_len[j] = starts[j + 1] - starts[j]
+ * (the last: to the end of the input); out_cap[j] = min(ISIZE, 1032 * in_len[j]) with ISIZE the little-endian dword at the end of
+ * that extent (0 for an extent below 18 bytes; 1032 : 1 is DEFLATE's maximum expansion, so a false start's garbage cannot ask for
+ * gigabytes); out_off[j] = out_base_off + out_cap[0] + ... + out_cap[j - 1], packed without alignment: the output is the members'
+ * concatenation; *total = the sum of all out_cap.  The sums are 64-bit, made on the device in a fixed order.
+ * flags: 0 -- in and the arrays are host memory; PZG_DEVICE_PTRS -- they are device memory.  nmembers and total are host memory in
+ * both forms and the calls return when they are filled: they run on a stream of the library's own, as pzg_index_scan does.  Any
+ * other flag, a context of several devices, m == 0 and in_len of 2^40 or more are PZG_RC_BAD_ARG; so, with host pointers, are
+ * descending starts and a start beyond in_len (device arrays are not read by the host: there such a start is taken as the
+ * nearest position that is neither, so that every extent lies inside the input).  Neither call reads anything but the aligned
+ * dwords that hold input bytes.
+ * Device memory, allocated for the call and freed before it returns: find -- 8 bytes per chunk (+ 8 per 4,096 chunks); layout -- 8
+ * bytes per 4,096 members.  The host-pointer forms also stage the input and the arrays in the context's arenas (in_len + 12 bytes
+ * per max_members; in_len + 40 bytes per member), which the context keeps.  PZG_RC_NO_MEMORY when the device does not have it.
+ * Not done here: a single member is still one wavefront's work (splitting a huge one with pzg_index_scan is up to the caller).
+ */
+PZG_API int pzg_gzip_find_members(pzg_ctx *ctx, const uint8_t *in, uint64_t in_len,
+        uint64_t chunk,                  /* 0: 64 KiB; below 64: PZG_RC_BAD_ARG */
+        uint64_t *starts, uint32_t *bsize, uint32_t max_members,
+        uint32_t *nmembers, uint32_t flags);
+PZG_API int pzg_gzip_layout(pzg_ctx *ctx, const uint8_t *in, uint64_t in_len,
+        const uint64_t *starts, uint32_t m, uint64_t out_base_off,
+        uint64_t *in_off, uint64_t *in_lenv, uint64_t *out_off,
+        uint64_t *out_cap, uint64_t *total, uint32_t flags);
+
+/*
  * decompressIncremental / ZlibDecoder (Zlib.hs:3-8, Monad.hs:163-197; driver Deflate.hs:30-48), batched: a pzg_decoder
  * is n suspended zlib decoders living on the device (a one-device context).  pzg_decoder_feed continues the decoders
  * idx[0..m) (idx = NULL: all n, m ignored) -- one launch, one wavefront per decoder -- as far as their input and

@@ -9,6 +9,7 @@ Only what the hot path needs lives here:
              over the same path; gzip members (row 4) are `gzip_decompress_many`
   zip.py     ZIP archives read and tested in one launch (raw DEFLATE members, sizes and CRC-32s from the central directory)
   indexed.py ONE large stream: an index of access points, every segment its own wavefront, reads at any offset
+  gzfile.py  a gzip FILE of many members (BGZF, WARC, concatenated .gz): members found on the device, a wavefront per member
   cxx/       the same module mirror in C++ (header-only)
 
 There is no CPU fallback: importing works anywhere, computing needs libpzg.so and a gfx950 device.
@@ -20,3 +21,4 @@ from .zlib import (  # noqa: F401
     gzip_decompress_many, raw_decompress, raw_decompress_many,
 )
 from .indexed import Index, adler32_combine, crc32_combine  # noqa: F401
+from .gzfile import MemberIndex, decompress_gzip_file  # noqa: F401

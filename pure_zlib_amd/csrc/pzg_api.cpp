@@ -1557,6 +1557,161 @@ int pzg_index_scan(pzg_ctx *ctx, const uint8_t *in, uint64_t in_len, uint64_t ch
     }
 }
 
+namespace {
+// scratch of one call, freed whatever way the call ends
+struct CallScratch {
+    void *p = nullptr;
+    ~CallScratch()
+    {
+        if (p) (void)hipFree(p);
+    }
+    int reserve(size_t bytes)
+    {
+        if (hipMalloc(&p, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            p = nullptr;
+            return PZG_RC_NO_MEMORY;
+        }
+        return PZG_RC_OK;
+    }
+};
+
+void lane_timed(Shard &sh, Lane &ln)
+{
+    float ms = -1.0f;
+    const bool ok = hipEventElapsedTime(&ms, ln.ev_t0, ln.ev_t1) == hipSuccess;
+    std::lock_guard<std::mutex> g(sh.mu);
+    sh.host_ms = ok ? (double)ms : -1.0;
+    sh.last_was_host = true;
+    sh.timed = true;
+}
+}  // namespace
+
+int pzg_gzip_find_members(pzg_ctx *ctx, const uint8_t *in, uint64_t in_len, uint64_t chunk, uint64_t *starts, uint32_t *bsize, uint32_t max_members,
+                          uint32_t *nmembers, uint32_t flags)
+{
+    if (!ctx_live(ctx)) return PZG_RC_BAD_ARG;
+    if (flags & ~PZG_DEVICE_PTRS) return PZG_RC_BAD_ARG;
+    if (ctx->shards.size() != 1) return PZG_RC_BAD_ARG;
+    if ((!in && in_len) || !nmembers || (max_members && (!starts || !bsize))) return PZG_RC_BAD_ARG;
+    if (in_len >> 40) return PZG_RC_BAD_ARG;
+    if (chunk == 0) chunk = 64u << 10;
+    if (chunk < 64u) return PZG_RC_BAD_ARG;
+    const uint64_t nchunks = in_len ? (in_len + chunk - 1u) / chunk : 1u;
+    const bool dev = (flags & PZG_DEVICE_PTRS) != 0;
+    Shard &sh = *ctx->shards[0];
+    Lane &ln = sh.lanes[0];
+    CallScratch scratch;
+    try {
+        std::lock_guard<std::mutex> lk(ln.mu);
+        HIP_TRY(ctx, hipSetDevice(sh.device));
+        int rc = lane_prepare(ctx, ln);
+        if (rc != PZG_RC_OK) return rc;
+        hipStream_t st = ln.s_k;
+        const uint8_t *d_in = in;
+        uint64_t *d_starts = starts;
+        uint32_t *d_bsize = bsize;
+        if (!dev) {
+            const size_t bs_off = pad256(8 * (size_t)max_members);
+            if ((rc = arena_reserve(ctx, ln.d_in[0], in_len + 64)) != PZG_RC_OK) return rc;
+            if ((rc = arena_reserve(ctx, ln.d_out[0], bs_off + 4 * (size_t)max_members + 64)) != PZG_RC_OK) return rc;
+            d_in = (const uint8_t *)ln.d_in[0].p;
+            d_starts = (uint64_t *)ln.d_out[0].p;
+            d_bsize = (uint32_t *)((uint8_t *)ln.d_out[0].p + bs_off);
+            if (in_len) HIP_TRY(ctx, hipMemcpyAsync(ln.d_in[0].p, in, in_len, hipMemcpyHostToDevice, st));
+        }
+        if ((rc = scratch.reserve(pzg::members_find_scratch_bytes(nchunks))) != PZG_RC_OK) return rc;
+        pzg::MemberArgs a{};
+        a.in = d_in;
+        a.in_len = in_len;
+        a.chunk = chunk;
+        a.nchunks = nchunks;
+        a.starts = d_starts;
+        a.bsize = d_bsize;
+        a.max_members = max_members;
+        HIP_TRY(ctx, hipEventRecord(ln.ev_t0, st));
+        HIP_TRY(ctx, pzg::launch_members_find(a, (uint8_t *)scratch.p, st));
+        HIP_TRY(ctx, hipEventRecord(ln.ev_t1, st));
+        uint64_t total = 0;
+        HIP_TRY(ctx, hipMemcpyAsync(&total, pzg::members_find_total(nchunks, (const uint8_t *)scratch.p), 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        *nmembers = total > 0xffffffffull ? 0xffffffffu : (uint32_t)total;
+        if (!dev) {
+            const size_t n = total < max_members ? (size_t)total : max_members;
+            if (n) HIP_TRY(ctx, hipMemcpy(starts, d_starts, 8 * n, hipMemcpyDeviceToHost));
+            if (n) HIP_TRY(ctx, hipMemcpy(bsize, d_bsize, 4 * n, hipMemcpyDeviceToHost));
+        }
+        lane_timed(sh, ln);
+        return PZG_RC_OK;
+    } catch (const std::bad_alloc &) {
+        return PZG_RC_NO_MEMORY;
+    }
+}
+
+int pzg_gzip_layout(pzg_ctx *ctx, const uint8_t *in, uint64_t in_len, const uint64_t *starts, uint32_t m, uint64_t out_base_off, uint64_t *in_off,
+                    uint64_t *in_lenv, uint64_t *out_off, uint64_t *out_cap, uint64_t *total, uint32_t flags)
+{
+    if (!ctx_live(ctx)) return PZG_RC_BAD_ARG;
+    if (flags & ~PZG_DEVICE_PTRS) return PZG_RC_BAD_ARG;
+    if (ctx->shards.size() != 1) return PZG_RC_BAD_ARG;
+    if (m == 0 || (!in && in_len) || !starts || !in_off || !in_lenv || !out_off || !out_cap || !total) return PZG_RC_BAD_ARG;
+    if (in_len >> 40) return PZG_RC_BAD_ARG;
+    const bool dev = (flags & PZG_DEVICE_PTRS) != 0;
+    if (!dev)
+        for (uint32_t j = 0; j < m; ++j)
+            if (starts[j] > in_len || (j && starts[j] < starts[j - 1])) return PZG_RC_BAD_ARG;
+    Shard &sh = *ctx->shards[0];
+    Lane &ln = sh.lanes[0];
+    CallScratch scratch;
+    try {
+        std::lock_guard<std::mutex> lk(ln.mu);
+        HIP_TRY(ctx, hipSetDevice(sh.device));
+        int rc = lane_prepare(ctx, ln);
+        if (rc != PZG_RC_OK) return rc;
+        hipStream_t st = ln.s_k;
+        pzg::LayoutArgs a{};
+        a.in = in;
+        a.in_len = in_len;
+        a.m = m;
+        a.out_base_off = out_base_off;
+        a.starts = starts;
+        a.in_off = in_off;
+        a.in_lenv = in_lenv;
+        a.out_off = out_off;
+        a.out_cap = out_cap;
+        const size_t row = pad256(8 * (size_t)m);
+        if (!dev) {
+            if ((rc = arena_reserve(ctx, ln.d_in[0], in_len + 64)) != PZG_RC_OK) return rc;
+            if ((rc = arena_reserve(ctx, ln.d_out[0], 5 * row)) != PZG_RC_OK) return rc;
+            uint8_t *d = (uint8_t *)ln.d_out[0].p;
+            a.in = (const uint8_t *)ln.d_in[0].p;
+            a.starts = (const uint64_t *)(d + 4 * row);
+            a.in_off = (uint64_t *)d;
+            a.in_lenv = (uint64_t *)(d + row);
+            a.out_off = (uint64_t *)(d + 2 * row);
+            a.out_cap = (uint64_t *)(d + 3 * row);
+            if (in_len) HIP_TRY(ctx, hipMemcpyAsync(ln.d_in[0].p, in, in_len, hipMemcpyHostToDevice, st));
+            HIP_TRY(ctx, hipMemcpyAsync(d + 4 * row, starts, 8 * (size_t)m, hipMemcpyHostToDevice, st));
+        }
+        if ((rc = scratch.reserve(pzg::members_layout_scratch_bytes(m))) != PZG_RC_OK) return rc;
+        HIP_TRY(ctx, hipEventRecord(ln.ev_t0, st));
+        HIP_TRY(ctx, pzg::launch_members_layout(a, (uint8_t *)scratch.p, st));
+        HIP_TRY(ctx, hipEventRecord(ln.ev_t1, st));
+        uint64_t sum = 0;
+        HIP_TRY(ctx, hipMemcpyAsync(&sum, pzg::members_layout_total(m, (const uint8_t *)scratch.p), 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        *total = sum;
+        if (!dev) {
+            uint64_t *const host[4] = {in_off, in_lenv, out_off, out_cap};
+            for (int k = 0; k < 4; ++k) HIP_TRY(ctx, hipMemcpy(host[k], (uint8_t *)ln.d_out[0].p + k * row, 8 * (size_t)m, hipMemcpyDeviceToHost));
+        }
+        lane_timed(sh, ln);
+        return PZG_RC_OK;
+    } catch (const std::bad_alloc &) {
+        return PZG_RC_NO_MEMORY;
+    }
+}
+
 int pzg_decompress_many_sharded(pzg_ctx *ctx, const pzg_device_batch *batches, uint32_t nbatches, uint32_t flags)
 {
     if (!ctx_live(ctx) || (!batches && nbatches)) return PZG_RC_BAD_ARG;

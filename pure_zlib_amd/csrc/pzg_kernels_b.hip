@@ -5,6 +5,7 @@
 //   inflate_raw_kernel<RB, *>       the raw instances
 //   inflate_seg_kernel              the segment instance (indexed streams), and index_windows_kernel beside it
 //   scan_find / scan_decode / scan_resolve_kernel   the parallel index scan (scan_core.h)
+//   member_* / sums_*_kernel        the members of a gzip file, found and laid out (member_core.h)
 //
 // SDWA forms save a vector instruction here and there (an extract folded into an add) but take their operands from registers
 // only: with the peephole on, a dozen small constants live in vector registers from the kernel's first line to its last.  The
@@ -12,6 +13,7 @@
 // have more state: without it the resumable kernel needs no scratch memory (12 spilled vector registers with it) and runs
 // 27 % faster (31.1 vs 24.4 GiB/s, bench.py's incremental leg), and the ring-11 gzip instance fits 72 registers (80 and one spill).
 #include "pzg_inflate_kernel.h"
+#include "member_core.h"
 #include "scan_core.h"
 
 namespace pzg {
@@ -227,6 +229,93 @@ hipError_t launch_scan(ScanArgs a, uint8_t *scratch, hipStream_t stream)
     hipLaunchKernelGGL(scan_resolve_kernel, dim3(1), dim3(1024), 0, stream, a);
     return hipGetLastError();
 }
+
+// ------------------------------------------------------------------------------------------------
+// The members of a gzip file (pzg_gzip_find_members, pzg_gzip_layout; member_core.h).  Bandwidth-bound sweeps and prefix sums: a
+// workgroup is one wave, the grids stride over their chunks, tiles and members.
+constexpr uint32_t MEMBER_GRID = 1u << 16;
+
+__global__ __launch_bounds__(64) void member_count_kernel(MemberArgs a)
+{
+    for (uint64_t k = blockIdx.x; k < a.nchunks; k += gridDim.x) {
+        const uint64_t n = Members::chunk_sweep<false>(a.in, a.in_len, a.chunk, k, 0u, nullptr, nullptr, 0u);
+        if (threadIdx.x == 0) a.counts[k] = n;
+    }
+}
+
+__global__ __launch_bounds__(64) void member_write_kernel(MemberArgs a)
+{
+    for (uint64_t k = blockIdx.x; k < a.nchunks; k += gridDim.x)
+        Members::chunk_sweep<true>(a.in, a.in_len, a.chunk, k, uni64(a.counts[k]), a.starts, a.bsize, a.max_members);
+}
+
+__global__ __launch_bounds__(64) void sums_tile_kernel(const uint64_t *x, uint64_t n, uint64_t *part)
+{
+    for (uint64_t t = blockIdx.x; t < Members::tiles(n); t += gridDim.x) Members::tile_sum(x, n, t, part);
+}
+
+__global__ __launch_bounds__(64) void sums_offsets_kernel(uint64_t *part, uint64_t ntiles, uint64_t base, uint64_t *total)
+{
+    Members::tile_offsets(part, ntiles, base, total);
+}
+
+__global__ __launch_bounds__(64) void sums_scan_kernel(const uint64_t *x, uint64_t n, const uint64_t *part, uint64_t *out)
+{
+    for (uint64_t t = blockIdx.x; t < Members::tiles(n); t += gridDim.x) Members::tile_scan(x, n, t, part, out);
+}
+
+__global__ __launch_bounds__(256) void member_layout_kernel(LayoutArgs a)
+{
+    Members::Input I;
+    I.init(a.in, a.in_len);
+    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < a.m; j += (uint64_t)gridDim.x * blockDim.x)
+        Members::member(I, a.starts, a.m, j, a.in_off, a.in_lenv, a.out_cap);
+}
+
+// out[i] = base + x[0] + ... + x[i - 1] (out may be x), *total = the sum of all n; part: tiles(n) entries of scratch
+static hipError_t launch_sums(const uint64_t *x, uint64_t n, uint64_t base, uint64_t *out, uint64_t *part, uint64_t *total, hipStream_t stream)
+{
+    const uint64_t nt = Members::tiles(n);
+    const dim3 grid((uint32_t)(nt < MEMBER_GRID ? nt : MEMBER_GRID));
+    hipLaunchKernelGGL(sums_tile_kernel, grid, dim3(64), 0, stream, x, n, part);
+    hipLaunchKernelGGL(sums_offsets_kernel, dim3(1), dim3(64), 0, stream, part, nt, base, total);
+    hipLaunchKernelGGL(sums_scan_kernel, grid, dim3(64), 0, stream, x, n, (const uint64_t *)part, out);
+    return hipGetLastError();
+}
+
+size_t members_find_scratch_bytes(uint64_t nchunks)
+{
+    // per chunk its count, then its offset (8 bytes); per 4,096 chunks their sum (8 bytes); the total: the figure include/pzg.h documents
+    return (size_t)(8u * nchunks + 8u * Members::tiles(nchunks) + 8u);
+}
+
+hipError_t launch_members_find(MemberArgs a, uint8_t *scratch, hipStream_t stream)
+{
+    a.counts = (uint64_t *)(void *)scratch;
+    uint64_t *part = a.counts + a.nchunks;
+    a.total = part + Members::tiles(a.nchunks);
+    const dim3 grid((uint32_t)(a.nchunks < MEMBER_GRID ? a.nchunks : MEMBER_GRID));
+    hipLaunchKernelGGL(member_count_kernel, grid, dim3(64), 0, stream, a);
+    hipError_t e = launch_sums(a.counts, a.nchunks, 0u, a.counts, part, a.total, stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(member_write_kernel, grid, dim3(64), 0, stream, a);
+    return hipGetLastError();
+}
+const uint64_t *members_find_total(uint64_t nchunks, const uint8_t *scratch)
+{
+    return (const uint64_t *)(const void *)scratch + nchunks + Members::tiles(nchunks);
+}
+
+size_t members_layout_scratch_bytes(uint64_t m) { return (size_t)(8u * Members::tiles(m) + 8u); }
+
+hipError_t launch_members_layout(const LayoutArgs &a, uint8_t *scratch, hipStream_t stream)
+{
+    uint64_t *part = (uint64_t *)(void *)scratch, *total = part + Members::tiles(a.m);
+    const uint64_t blocks = (a.m + 255u) / 256u;
+    hipLaunchKernelGGL(member_layout_kernel, dim3((uint32_t)(blocks < MEMBER_GRID ? blocks : MEMBER_GRID)), dim3(256), 0, stream, a);
+    return launch_sums(a.out_cap, a.m, a.out_base_off, a.out_off, part, total, stream);
+}
+const uint64_t *members_layout_total(uint64_t m, const uint8_t *scratch) { return (const uint64_t *)(const void *)scratch + Members::tiles(m); }
 
 // ------------------------------------------------------------------------------------------------
 // The resumable decoder (decompressIncremental, Monad.hs:163-197): one launch continues a batch of suspended decoders,

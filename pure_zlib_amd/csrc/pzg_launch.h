@@ -126,6 +126,31 @@ struct ScanArgs {
 size_t scan_scratch_bytes(uint32_t nchunks);
 hipError_t launch_scan(ScanArgs a, uint8_t *scratch, hipStream_t stream);
 
+// the members of a gzip file (pzg_kernels_b.hip, member_core.h).  The caller fills in what is above the line; `scratch`:
+// members_find_scratch_bytes(nchunks) bytes of device memory, 8-byte aligned; the count of candidates lands at members_find_total().
+struct MemberArgs {
+    const uint8_t *in;
+    uint64_t in_len, chunk, nchunks;
+    uint64_t *starts;      // max_members
+    uint32_t *bsize;       // max_members
+    uint64_t max_members;
+    // ----
+    uint64_t *counts, *total;
+};
+size_t members_find_scratch_bytes(uint64_t nchunks);
+hipError_t launch_members_find(MemberArgs a, uint8_t *scratch, hipStream_t stream);
+const uint64_t *members_find_total(uint64_t nchunks, const uint8_t *scratch);
+// ... and their layout: m entries each; scratch: members_layout_scratch_bytes(m) bytes, the sum of the rooms at members_layout_total()
+struct LayoutArgs {
+    const uint8_t *in;
+    uint64_t in_len, m, out_base_off;
+    const uint64_t *starts;
+    uint64_t *in_off, *in_lenv, *out_off, *out_cap;
+};
+size_t members_layout_scratch_bytes(uint64_t m);
+hipError_t launch_members_layout(const LayoutArgs &a, uint8_t *scratch, hipStream_t stream);
+const uint64_t *members_layout_total(uint64_t m, const uint8_t *scratch);
+
 // partials: 3 * 4 * ceil(max_waves / 4) uint32 of device scratch
 hipError_t launch_adler32(const uint8_t *buf, uint64_t len, uint32_t init, uint32_t *partials, uint32_t max_waves,
                           uint32_t *out, hipStream_t stream);

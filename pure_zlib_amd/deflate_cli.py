@@ -17,6 +17,10 @@ deflate --index foo.pzi --parallel foo.z               the same without the sequ
                                                        (Index.build_parallel), the file is decoded by segments and verified
 deflate --use-index foo.pzi [--range OFF:LEN] foo.z    decodes foo with a wavefront per segment of the index and writes it; with
                                                        --range only the segments that cover LEN bytes from OFF, written to stdout
+
+Members mode (pure_zlib_amd/gzfile.py), for a gzip file of MANY members -- BGZF, WARC, `cat a.gz b.gz`:
+deflate --members foo.gz                               finds the members on the device, decodes them with a wavefront per member in
+                                                       one launch and writes foo; "ERROR: <show e>" for a file that does not decode
 """
 import sys
 
@@ -121,10 +125,31 @@ def run_indexed(args) -> None:
         print("ERROR: " + r.value.show())
 
 
+def run_members(args) -> None:
+    """Members mode: --members NAME.gz."""
+    from .gzfile import decompress_gzip_file
+    if len(args) != 1:
+        print("USAGE: deflate --members filename")
+        return
+    if not args[0].endswith(".gz"):
+        print("Unexpected file name.")
+        return
+    with open(args[0], "rb") as f:
+        r = decompress_gzip_file(f.read())
+    if r.is_right():
+        with open(args[0][:-3], "wb") as out:
+            out.write(r.value)
+    else:
+        print("ERROR: " + r.value.show())
+
+
 def main(argv=None) -> int:
     args = sys.argv[1:] if argv is None else argv
     if args and args[0] == "--many":
         run_many(args[1:])
+        return 0
+    if args and args[0] == "--members":
+        run_members(args[1:])
         return 0
     if args and args[0] in ("--index", "--use-index"):
         run_indexed(args)
