@@ -2120,6 +2120,9 @@ struct Decoder {
 #ifndef PZG_SEQ_GROUP
 #define PZG_SEQ_GROUP 8
 #endif
+#ifndef PZG_TOP_MOVES
+#define PZG_TOP_MOVES 1  // strip_top(): the reader's 64-bit selects as moves under EXEC (0: as selects)
+#endif
     // A lane's region of the scratch, byte offsets: 16 bytes of slack | the literal area (STRIP_TMAX bytes from REG_LITA on) |
     // SEQ_G records of slack | the record area (STRIP_TMAX dwords from REG_RECA on).  The slack in front of an area takes the
     // lane's last, partial group, which is stored as the lane's LAST 16 literals / SEQ_G records wherever they end.
@@ -2334,10 +2337,41 @@ struct Decoder {
     // the top of a step: 64 bits on if the position says so, and the pair behind W1 asked for (again)
     PZG_FN static void strip_top(const uint32_t *sp, uint32_t maxdw, uint64_t &w0, uint64_t &w1, uint64_t &t, uint64_t &tn, uint32_t &r, uint32_t &nx, bool &pend)
     {
-        t = pend ? tn : t;
         const bool sh = r >= 64u;
-        w0 = sh ? w1 : w0;
-        w1 = sh ? t : w1;
+#if PZG_DEVICE_PASS && PZG_TOP_MOVES
+        // (the three 64-bit selects as six register moves under the lanes' masks in EXEC: a v_cndmask costs the vector port twice
+        // what a v_mov does -- profiles/r04_op_cost.txt --, and the masks are in scalar registers already.  Not in the resumable
+        // instance: it costs some twenty scalar spills outside the loops, which that kernel's budget does not have)
+        // Why EXEC may be rewritten here without `volatile`: the statement has no effect but its outputs (a pure function of its
+        // inputs); both masks are ballots, so subsets of the EXEC that is live around it, which the last instruction restores;
+        // device asm is convergent to the compiler, so it is not moved across control flow that depends on the lanes.  The two
+        // halves of TN are read (first two moves) before any output that another operand could share a register with is written,
+        // and an input shares a register with a "+v" operand only when both hold the same value.
+        if (!RES) {
+            uint32_t w0l = (uint32_t)w0, w0h = (uint32_t)(w0 >> 32), w1l = (uint32_t)w1, w1h = (uint32_t)(w1 >> 32), tl = (uint32_t)t, th = (uint32_t)(t >> 32);
+            uint64_t sv;
+            asm("s_mov_b64 %6, exec\n\t"
+                "s_mov_b64 exec, %9\n\t"
+                "v_mov_b32 %4, %7\n\t"
+                "v_mov_b32 %5, %8\n\t"
+                "s_mov_b64 exec, %10\n\t"
+                "v_mov_b32 %0, %2\n\t"
+                "v_mov_b32 %1, %3\n\t"
+                "v_mov_b32 %2, %4\n\t"
+                "v_mov_b32 %3, %5\n\t"
+                "s_mov_b64 exec, %6"
+                : "+v"(w0l), "+v"(w0h), "+v"(w1l), "+v"(w1h), "+v"(tl), "+v"(th), "=&s"(sv)
+                : "v"((uint32_t)tn), "v"((uint32_t)(tn >> 32)), "s"(__builtin_amdgcn_ballot_w64(pend)), "s"(__builtin_amdgcn_ballot_w64(sh)));
+            w0 = (uint64_t)w0l | ((uint64_t)w0h << 32);
+            w1 = (uint64_t)w1l | ((uint64_t)w1h << 32);
+            t = (uint64_t)tl | ((uint64_t)th << 32);
+        } else
+#endif
+        {
+            t = pend ? tn : t;
+            w0 = sh ? w1 : w0;
+            w1 = sh ? t : w1;
+        }
         r &= 63u;
         nx += sh ? 2u : 0u;
         // (the lanes that did not move ask for the span's first pair: one cache line for all of them -- asking for their own pair
