@@ -12,6 +12,16 @@
 // Host-pointer batches are packed (no gaps travel over PCIe), launched longest stream first, and flow through the
 // lane in index ranges: pack + H2D of range c+1, the kernel on range c and D2H + copy-out of range c-1 overlap, and
 // the two PCIe directions run on their own streams.
+//
+// Sections, in the file's order:
+//   errors            hip_fail / HIP_TRY / PIPE_TRY, and guarded(): the one place where a C++ exception becomes a return code
+//   resources         arenas, pinned staging, lanes, shards, the context
+//   a call's pieces   LaneCall (a synchronous call on lane 0: lock, prepare, kernel span, drained if it leaves early), CallScratch,
+//                     stage_input, copy_back_windows; MetaBlock (the packed per-stream arrays) and the two inflate_args();
+//                     extents_ok / dict_extents_ok
+//   paths             launch_device (device pointers), host_path (pipelined ranges), dict_path (dictionaries, segments)
+//   entry points      init and options, decompress_many*, the index calls, the gzip member calls, the sharded call,
+//                     resumable decoders, Adler-32, timing and texts
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -172,6 +182,36 @@ int hip_fail(pzg_ctx *ctx, hipError_t e, const char *what)
         if (e_ != hipSuccess) return hip_fail(ctx, e_, #call); \
     } while (0)
 
+// The pipelined paths (host_path, a large pzg_decoder_feed) issue nothing more after the first failure and report it when their
+// threads have been joined: it is kept in the locals `herr` / `hwhat`.
+#define PIPE_TRY(call)                             \
+    do {                                           \
+        if (herr == hipSuccess) {                  \
+            herr = (call);                         \
+            if (herr != hipSuccess) hwhat = #call; \
+        }                                          \
+    } while (0)
+
+// The exception boundary of the C ABI: the body of every entry point that can throw runs in here.
+template <class F>
+int guarded(pzg_ctx *ctx, const char *name, F &&body)
+{
+    try {
+        return body();
+    } catch (const std::bad_alloc &) {
+        return PZG_RC_NO_MEMORY;
+    } catch (...) {  // (in practice a std::system_error from a mutex or a thread)
+        try {
+            if (ctx) {
+                std::lock_guard<std::mutex> g(ctx->err_mu);
+                ctx->last_error = std::string("C++ exception inside ") + name;
+            }
+        } catch (...) {
+        }
+        return PZG_RC_HIP_ERROR;
+    }
+}
+
 int arena_reserve(pzg_ctx *ctx, Arena &a, size_t bytes)
 {
     bytes = (bytes + 255u) & ~(size_t)255u;
@@ -192,8 +232,6 @@ int arena_reserve(pzg_ctx *ctx, Arena &a, size_t bytes)
 // The kernels' scratch for one launch of n streams into arena `a`: as many whole stream-wave slices as the launch can use and the
 // context's cap (PZG_OPT_SCRATCH_BYTES, shared evenly by the arenas a shard can hold) allows.  Failing is tolerated -- the
 // launch then decodes by windows alone, slower and never wrong -- so nothing is recorded as an error.
-void strip_for_launch(pzg_ctx *ctx, Arena &a, int num_cus, uint32_t n, uint32_t gzip, pzg::InflateArgs &args);
-
 void strip_for_launch(pzg_ctx *ctx, Arena &a, int num_cus, uint32_t n, uint32_t gzip, pzg::InflateArgs &args)
 {
     args.strip = nullptr;
@@ -318,6 +356,102 @@ void lane_drain(Lane &ln)
     if (ln.s_up) (void)hipStreamSynchronize(ln.s_up);
     if (ln.s_k) (void)hipStreamSynchronize(ln.s_k);
     if (ln.s_dn) (void)hipStreamSynchronize(ln.s_dn);
+}
+
+// The kernel span of the call that holds lane `ln`, measured by the call itself on its own lane's events (pzg_last_kernel_ms): calls
+// of other threads on other lanes cannot get between the two.  wait_t1: the caller has not synchronised with ev_t1's stream.
+void lane_timed(Shard &sh, Lane &ln, bool wait_t1 = false)
+{
+    float ms = -1.0f;
+    const bool ok = (!wait_t1 || hipEventSynchronize(ln.ev_t1) == hipSuccess) && hipEventElapsedTime(&ms, ln.ev_t0, ln.ev_t1) == hipSuccess;
+    std::lock_guard<std::mutex> g(sh.mu);
+    sh.host_ms = ok ? (double)ms : -1.0;
+    sh.last_was_host = true;
+    sh.timed = true;
+}
+
+// device scratch of one call, freed whatever way the call ends
+struct CallScratch {
+    void *p = nullptr;
+    ~CallScratch()
+    {
+        if (p) (void)hipFree(p);
+    }
+    int reserve(size_t bytes)
+    {
+        if (hipMalloc(&p, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            p = nullptr;
+            return PZG_RC_NO_MEMORY;
+        }
+        return PZG_RC_OK;
+    }
+};
+
+// The scope of a synchronous call on one lane (dict_path, the index calls, the gzip member calls): lane 0 of the shard, locked and
+// prepared; everything the call enqueues goes to `st`, with begin_timed() / end_timed() around its launches, and finish() waits for
+// it all and stores the kernel span.  A call that leaves before finish() -- an error return, an exception -- has its lane drained
+// first: no copy stays in flight into the caller's memory, into the call's own variables or into scratch about to be freed.  So
+// whatever the call's copies touch and has a destructor (a CallScratch, a vector) is declared BEFORE the LaneCall.
+struct LaneCall {
+    pzg_ctx *ctx;
+    Shard &sh;
+    Lane &ln;
+    std::lock_guard<std::mutex> lk;
+    hipStream_t st = nullptr;
+    bool finished = false;
+    int rc;  // not PZG_RC_OK: the lane could not be prepared, the call returns this
+    LaneCall(pzg_ctx *c, Shard &s) : ctx(c), sh(s), ln(s.lanes[0]), lk(ln.mu), rc(prepare()) {}
+    ~LaneCall()
+    {
+        if (!finished) lane_drain(ln);
+    }
+    hipError_t begin_timed() { return hipEventRecord(ln.ev_t0, st); }
+    hipError_t end_timed() { return hipEventRecord(ln.ev_t1, st); }
+    int finish()
+    {
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        lane_timed(sh, ln);
+        finished = true;
+        return PZG_RC_OK;
+    }
+
+private:
+    int prepare()
+    {
+        HIP_TRY(ctx, hipSetDevice(sh.device));
+        const int r = lane_prepare(ctx, ln);
+        st = ln.s_k;
+        return r;
+    }
+};
+
+// The input of a single-stream call where the kernels read it: the caller's own pointer (dev: PZG_DEVICE_PTRS), else the lane's
+// d_in[0], uploaded on the call's stream.
+int stage_input(LaneCall &call, const uint8_t *in, uint64_t in_len, bool dev, const uint8_t *&d_in)
+{
+    d_in = in;
+    if (dev) return PZG_RC_OK;
+    Arena &a = call.ln.d_in[0];
+    const int rc = arena_reserve(call.ctx, a, in_len + 64);
+    if (rc != PZG_RC_OK) return rc;
+    d_in = (const uint8_t *)a.p;
+    if (in_len) HIP_TRY(call.ctx, hipMemcpyAsync(a.p, in, in_len, hipMemcpyHostToDevice, call.st));
+    return PZG_RC_OK;
+}
+
+// The windows of an index's first np points, from the device's slots to the caller's (host pointers; the stream is idle).  A point
+// below 32768 has a shorter window, at the end of its slot: the front of the caller's slot stays as it is.  out_pos ascends, so
+// these are the first few points; whole slots follow in one copy.
+int copy_back_windows(pzg_ctx *ctx, const pzg_index_point *points, size_t np, uint8_t *windows, const uint8_t *d_win)
+{
+    size_t k = 0;
+    for (; k < np && points[k].out_pos < 32768u; ++k) {
+        const size_t at = 32768u * k + (32768u - (size_t)points[k].out_pos);
+        HIP_TRY(ctx, hipMemcpy(windows + at, d_win + at, (size_t)points[k].out_pos, hipMemcpyDeviceToHost));
+    }
+    if (k < np) HIP_TRY(ctx, hipMemcpy(windows + 32768u * k, d_win + 32768u * k, 32768u * (np - k), hipMemcpyDeviceToHost));
+    return PZG_RC_OK;
 }
 
 int shard_create(pzg_ctx *ctx, int device, std::unique_ptr<Shard> &out)
@@ -483,6 +617,7 @@ int launch_device(pzg_ctx *ctx, Shard &sh, pzg::InflateArgs a, uint32_t flags)
 }
 
 // ---- the host-pointer path on one shard, for the streams idx[0..m) of the caller's batch -----------------------
+// (a batch's arrays as the caller passed them: host pointers here; device pointers where a call only makes launch arguments of them)
 struct HostBatch {
     const uint8_t *in_base;
     const uint64_t *in_off, *in_len;
@@ -505,6 +640,111 @@ struct Range {
 
 inline size_t pad16(size_t x) { return (x + 15u) & ~(size_t)15u; }
 inline size_t pad256(size_t x) { return (x + 255u) & ~(size_t)255u; }
+
+// The launch arguments of n streams whose arrays are the caller's own (device pointers), with the optional dictionary and segment arrays.
+pzg::InflateArgs inflate_args(const HostBatch &b, uint32_t n, const uint8_t *dict_base = nullptr, const uint64_t *dict_off = nullptr,
+                              const uint64_t *dict_len = nullptr, const uint8_t *start_bit = nullptr, const uint64_t *end_bit = nullptr)
+{
+    pzg::InflateArgs a{};
+    a.in_base = b.in_base;
+    a.in_off = b.in_off;
+    a.in_len = b.in_len;
+    a.out_base = b.out_base;
+    a.out_off = b.out_off;
+    a.out_cap = b.out_cap;
+    a.out_len = b.out_len;
+    a.status = b.status;
+    a.detail = b.detail;
+    a.in_used = b.in_used;
+    a.adler = b.adler;
+    a.n = n;
+    if (dict_base) {
+        a.dict_base = dict_base;
+        a.dict_off = dict_off;
+        a.dict_len = dict_len;
+    }
+    if (start_bit) {
+        a.seg = 1u;
+        a.seg_start_bit = start_bit;
+        a.seg_end_bit = end_bit;
+    }
+    return a;
+}
+
+// The packed meta block of n streams, the same bytes on the host and on the device -- this is the one place that knows them:
+//   extents   u64[n] each: in_off | in_len | out_off | out_cap, and with dictionaries | dict_off | dict_len      (host -> device)
+//   results   out_len u64[n] | in_used u64[n] | status i32[n] | adler u32[n] | detail u32[2n]: 32 n bytes          (device -> host)
+//   segments  end_bit u64[n] | start_bit u8[n] (the segment path alone)                                           (host -> device)
+// 64 n bytes without dictionaries (host_path's ranges, the index build's one stream), 89 n with both (dict_path).
+struct MetaBlock {
+    uint64_t *in_off, *in_len, *out_off, *out_cap, *dict_off = nullptr, *dict_len = nullptr, *out_len, *in_used;
+    int32_t *status;
+    uint32_t *adler, *detail;
+    uint64_t *end_bit;
+    uint8_t *start_bit;
+    size_t extent_bytes;  // the results start here
+    MetaBlock(uint8_t *base, size_t n, bool dict) : extent_bytes((dict ? 48 : 32) * n)
+    {
+        in_off = (uint64_t *)base;
+        in_len = in_off + n;
+        out_off = in_len + n;
+        out_cap = out_off + n;
+        if (dict) {
+            dict_off = out_cap + n;
+            dict_len = dict_off + n;
+        }
+        out_len = (uint64_t *)(base + extent_bytes);
+        in_used = out_len + n;
+        status = (int32_t *)(in_used + n);
+        adler = (uint32_t *)(status + n);
+        detail = adler + n;
+        end_bit = (uint64_t *)(detail + 2 * n);
+        start_bit = (uint8_t *)(end_bit + n);
+    }
+};
+
+// The launch arguments of n streams laid out by a meta block on the device; dictionaries lie in the input arena beside the streams.
+pzg::InflateArgs inflate_args(const MetaBlock &m, uint32_t n, const uint8_t *in_base, uint8_t *out_base, bool segments = false)
+{
+    const HostBatch b{in_base, m.in_off, m.in_len, out_base, m.out_off, m.out_cap, m.out_len, m.status, m.detail, m.in_used, m.adler, 0u};
+    return inflate_args(b, n, m.dict_off ? in_base : nullptr, m.dict_off, m.dict_len, segments ? m.start_bit : nullptr, m.end_bit);
+}
+
+// stream q of a meta block's results, into the caller's arrays at i
+inline void store_results(const HostBatch &b, size_t i, const MetaBlock &h, size_t q)
+{
+    b.out_len[i] = h.out_len[q];
+    b.status[i] = h.status[q];
+    if (b.in_used) b.in_used[i] = h.in_used[q];
+    if (b.adler) b.adler[i] = h.adler[q];
+    if (b.detail) {
+        b.detail[2 * i] = h.detail[2 * q];
+        b.detail[2 * i + 1] = h.detail[2 * q + 1];
+    }
+}
+
+// Host-pointer extents a call can work with: a wrapped offset + length would size an arena far too small, the kernels' sizes have
+// 40 bits, and output needs somewhere to go.
+bool extents_ok(const HostBatch &b, uint32_t n)
+{
+    bool any_out = false;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (b.in_off[i] + b.in_len[i] < b.in_off[i] || b.out_off[i] + b.out_cap[i] < b.out_off[i]) return false;
+        if ((b.in_len[i] >> 40) || (b.out_cap[i] >> 40)) return false;
+        any_out |= b.out_cap[i] != 0;
+    }
+    return !any_out || b.out_base;
+}
+
+// ... and the dictionaries' extents; *any: one of them is not empty
+bool dict_extents_ok(const uint64_t *dict_off, const uint64_t *dict_len, uint32_t n, bool *any = nullptr)
+{
+    for (uint32_t i = 0; i < n; ++i) {
+        if (dict_off[i] + dict_len[i] < dict_off[i] || (dict_len[i] >> 32)) return false;
+        if (any && dict_len[i]) *any = true;
+    }
+    return true;
+}
 
 // The host-pointer path.  Two forms:
 //   staged (default)    pageable caller memory: the streams are packed into page-locked staging (no gaps travel), launched
@@ -624,26 +864,11 @@ int host_path(pzg_ctx *ctx, Shard &sh, const HostBatch &b, const uint32_t *idx, 
     strip_for_launch(ctx, ln.d_strip, sh.num_cus, (uint32_t)max_n, (b.flags & PZG_GZIP) ? 1u : 0u, strip_args);
     const unsigned helpers = (!pinned && (tot_in + tot_out) >= (32ull << 20)) ? ctx->helpers->size() : 1u;
 
-    auto meta_ptrs = [&](uint8_t *base, size_t nn, uint64_t *&ioff, uint64_t *&ilen, uint64_t *&ooff, uint64_t *&ocap, uint64_t *&olen,
-                         uint64_t *&used, int32_t *&st, uint32_t *&ad, uint32_t *&det) {
-        ioff = (uint64_t *)base;
-        ilen = ioff + nn;
-        ooff = ilen + nn;
-        ocap = ooff + nn;
-        olen = ocap + nn;
-        used = olen + nn;
-        st = (int32_t *)(used + nn);
-        ad = (uint32_t *)(st + nn);
-        det = ad + nn;
-    };
-
     // lay out the range's extents; staged: pack its streams into the pinned input slot
     auto pack = [&](const Range &r, int s) {
         const size_t nn = r.hi - r.lo;
-        uint64_t *ioff, *ilen, *ooff, *ocap, *olen, *used;
-        int32_t *st;
-        uint32_t *ad, *det;
-        meta_ptrs(ln.h_meta[s].p, nn, ioff, ilen, ooff, ocap, olen, used, st, ad, det);
+        const MetaBlock h(ln.h_meta[s].p, nn, false);
+        uint64_t *const ioff = h.in_off, *const ilen = h.in_len, *const ooff = h.out_off, *const ocap = h.out_cap;
         if (pinned) {  // the caller's own layout, relative to the start of the batch's spans
             for (size_t q = 0; q < nn; ++q) {
                 const uint32_t i = idx[r.lo + q];
@@ -676,25 +901,15 @@ int host_path(pzg_ctx *ctx, Shard &sh, const HostBatch &b, const uint32_t *idx, 
     // hand a finished range to the caller: results, and (staged) the decoded bytes out of the pinned output slot
     auto unpack = [&](const Range &r, int s) {
         const size_t nn = r.hi - r.lo;
-        uint64_t *ioff, *ilen, *ooff, *ocap, *olen, *used;
-        int32_t *st;
-        uint32_t *ad, *det;
-        meta_ptrs(ln.h_meta[s].p, nn, ioff, ilen, ooff, ocap, olen, used, st, ad, det);
+        const MetaBlock h(ln.h_meta[s].p, nn, false);
         const uint8_t *src = pinned ? nullptr : ln.h_out[s].p;
         ctx->helpers->run(helpers, [&](unsigned t, unsigned parts) {
             const size_t q0 = nn * t / parts, q1 = nn * (t + 1) / parts;
             for (size_t q = q0; q < q1; ++q) {
                 const uint32_t i = idx[r.lo + q];
-                b.out_len[i] = olen[q];
-                b.status[i] = st[q];
-                if (b.in_used) b.in_used[i] = used[q];
-                if (b.adler) b.adler[i] = ad[q];
-                if (b.detail) {
-                    b.detail[2 * (size_t)i] = det[2 * q];
-                    b.detail[2 * (size_t)i + 1] = det[2 * q + 1];
-                }
-                const uint64_t nb = olen[q] < ocap[q] ? olen[q] : ocap[q];
-                if (src && nb) memcpy(b.out_base + b.out_off[i], src + ooff[q], nb);
+                store_results(b, i, h, q);
+                const uint64_t nb = std::min(h.out_len[q], h.out_cap[q]);
+                if (src && nb) memcpy(b.out_base + b.out_off[i], src + h.out_off[q], nb);
             }
         });
     };
@@ -704,14 +919,6 @@ int host_path(pzg_ctx *ctx, Shard &sh, const HostBatch &b, const uint32_t *idx, 
     double t_pack = 0, t_unpack = 0, t_wait = 0;
     auto tick = [] { return std::chrono::steady_clock::now(); };
     auto since = [](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
-#define LANE_TRY(call)                 \
-    do {                               \
-        if (herr == hipSuccess) {      \
-            herr = (call);             \
-            if (herr != hipSuccess) hwhat = #call; \
-        }                              \
-    } while (0)
-
     // Two host threads per call: this one packs and issues range after range; a second one waits for each range's
     // download and copies it out to the caller.  A slot is reused once its previous occupant has been copied out.
     const size_t R = rg.size();
@@ -787,32 +994,16 @@ int host_path(pzg_ctx *ctx, Shard &sh, const HostBatch &b, const uint32_t *idx, 
         t_pack += since(tp);
         uint8_t *dm = (uint8_t *)ln.d_meta[s].p;
         uint8_t *din = (uint8_t *)ln.d_in[pinned ? 0 : s].p, *dout = (uint8_t *)ln.d_out[pinned ? 0 : s].p;
-        LANE_TRY(hipMemcpyAsync(dm, ln.h_meta[s].p, 32 * nn, hipMemcpyHostToDevice, s_up));  // the four extent arrays
+        PIPE_TRY(hipMemcpyAsync(dm, ln.h_meta[s].p, 32 * nn, hipMemcpyHostToDevice, s_up));  // the four extent arrays
         if (r.in_bytes) {
-            if (pinned) LANE_TRY(hipMemcpyAsync(din + (r.in_lo - g_in_lo), b.in_base + r.in_lo, r.in_bytes, hipMemcpyHostToDevice, s_up));
-            else LANE_TRY(hipMemcpyAsync(din, ln.h_in[s].p, r.in_bytes, hipMemcpyHostToDevice, s_up));
+            if (pinned) PIPE_TRY(hipMemcpyAsync(din + (r.in_lo - g_in_lo), b.in_base + r.in_lo, r.in_bytes, hipMemcpyHostToDevice, s_up));
+            else PIPE_TRY(hipMemcpyAsync(din, ln.h_in[s].p, r.in_bytes, hipMemcpyHostToDevice, s_up));
         }
         if (R > 1) {
-            LANE_TRY(hipEventRecord(ln.ev_up[s], s_up));
-            LANE_TRY(hipStreamWaitEvent(ln.s_k, ln.ev_up[s], 0));
+            PIPE_TRY(hipEventRecord(ln.ev_up[s], s_up));
+            PIPE_TRY(hipStreamWaitEvent(ln.s_k, ln.ev_up[s], 0));
         }
-        pzg::InflateArgs a{};
-        uint64_t *ioff, *ilen, *ooff, *ocap, *olen, *used;
-        int32_t *st;
-        uint32_t *ad, *det;
-        meta_ptrs(dm, nn, ioff, ilen, ooff, ocap, olen, used, st, ad, det);
-        a.in_base = din;
-        a.out_base = dout;
-        a.in_off = ioff;
-        a.in_len = ilen;
-        a.out_off = ooff;
-        a.out_cap = ocap;
-        a.out_len = olen;
-        a.in_used = used;
-        a.status = st;
-        a.adler = ad;
-        a.detail = det;
-        a.n = (uint32_t)nn;
+        pzg::InflateArgs a = inflate_args(MetaBlock(dm, nn, false), (uint32_t)nn, din, dout);
         a.counter = ln.d_counter;
         a.strip = strip_args.strip;
         a.strip_waves = strip_args.strip_waves;
@@ -824,24 +1015,24 @@ int host_path(pzg_ctx *ctx, Shard &sh, const HostBatch &b, const uint32_t *idx, 
 #if defined(PZG_PROFILE)
         a.prof_out = ctx->prof_buf ? (uint64_t *)ctx->prof_buf + 16 * (size_t)r.lo : nullptr;
 #endif
-        if (c == 0) LANE_TRY(hipEventRecord(ln.ev_t0, ln.s_k));
+        if (c == 0) PIPE_TRY(hipEventRecord(ln.ev_t0, ln.s_k));
         if (pinned && r.mixed) {  // the caller's order stays: the longest streams are launched first through a permutation
             uint32_t *ord = (uint32_t *)ln.d_ord[s].p;
-            LANE_TRY(pzg::launch_order(ocap, a.n, ord + 256, ord, ln.s_k));
+            PIPE_TRY(pzg::launch_order(a.out_cap, a.n, ord + 256, ord, ln.s_k));
             a.order = ord + 256;
         }
-        LANE_TRY(pzg::launch_inflate(a, ctx->ring_bits, sh.num_cus, ln.s_k));
-        if (c + 1 == R) LANE_TRY(hipEventRecord(ln.ev_t1, ln.s_k));
+        PIPE_TRY(pzg::launch_inflate(a, ctx->ring_bits, sh.num_cus, ln.s_k));
+        if (c + 1 == R) PIPE_TRY(hipEventRecord(ln.ev_t1, ln.s_k));
         if (R > 1) {
-            LANE_TRY(hipEventRecord(ln.ev_k[s], ln.s_k));
-            LANE_TRY(hipStreamWaitEvent(s_dn, ln.ev_k[s], 0));
+            PIPE_TRY(hipEventRecord(ln.ev_k[s], ln.s_k));
+            PIPE_TRY(hipStreamWaitEvent(s_dn, ln.ev_k[s], 0));
         }
-        LANE_TRY(hipMemcpyAsync(ln.h_meta[s].p + 32 * nn, dm + 32 * nn, 32 * nn, hipMemcpyDeviceToHost, s_dn));  // results
+        PIPE_TRY(hipMemcpyAsync(ln.h_meta[s].p + 32 * nn, dm + 32 * nn, 32 * nn, hipMemcpyDeviceToHost, s_dn));  // results
         if (r.out_bytes) {
-            if (pinned) LANE_TRY(hipMemcpyAsync(b.out_base + r.out_lo, dout + (r.out_lo - g_out_lo), r.out_bytes, hipMemcpyDeviceToHost, s_dn));
-            else LANE_TRY(hipMemcpyAsync(ln.h_out[s].p, dout, r.out_bytes, hipMemcpyDeviceToHost, s_dn));
+            if (pinned) PIPE_TRY(hipMemcpyAsync(b.out_base + r.out_lo, dout + (r.out_lo - g_out_lo), r.out_bytes, hipMemcpyDeviceToHost, s_dn));
+            else PIPE_TRY(hipMemcpyAsync(ln.h_out[s].p, dout, r.out_bytes, hipMemcpyDeviceToHost, s_dn));
         }
-        LANE_TRY(hipEventRecord(ln.ev_dn[s], s_dn));
+        PIPE_TRY(hipEventRecord(ln.ev_dn[s], s_dn));
         if (herr == hipSuccess) {
             {
                 std::lock_guard<std::mutex> g(pm);
@@ -860,20 +1051,11 @@ int host_path(pzg_ctx *ctx, Shard &sh, const HostBatch &b, const uint32_t *idx, 
         herr = derr;
         hwhat = derr == hipErrorOutOfMemory ? "copy-out of a range (out of memory)" : "hipEventSynchronize (download)";
     }
-#undef LANE_TRY
     if (herr != hipSuccess) {
         lane_drain(ln);
         return hip_fail(ctx, herr, hwhat);
     }
-    {   // the call's kernel span, measured by the call itself on its own lane's events (pzg_last_kernel_ms): calls of
-        // other threads on other lanes cannot get between the two
-        float ms = -1.0f;
-        const bool ok = hipEventSynchronize(ln.ev_t1) == hipSuccess && hipEventElapsedTime(&ms, ln.ev_t0, ln.ev_t1) == hipSuccess;
-        std::lock_guard<std::mutex> g(sh.mu);
-        sh.host_ms = ok ? (double)ms : -1.0;
-        sh.last_was_host = true;
-        sh.timed = true;
-    }
+    lane_timed(sh, ln, true);  // (ev_t1 is on s_k: the downloads that were waited for are on s_dn)
     if (trace)
         fprintf(stderr, "[pzg] host path%s: %u streams, %.1f MiB in, %.1f MiB out, %zu range(s), %u helper thread(s): %.1f ms "
                 "(packing %.1f on the issuing thread; on the draining thread: waiting for downloads %.1f, copy-out %.1f)\n", pinned ? " (pinned arenas)" : "",
@@ -887,94 +1069,55 @@ int host_path(pzg_ctx *ctx, Shard &sh, const HostBatch &b, const uint32_t *idx, 
 int dict_path(pzg_ctx *ctx, Shard &sh, const HostBatch &b, const uint8_t *dict_base, const uint64_t *dict_off, const uint64_t *dict_len,
               uint32_t n, const uint8_t *start_bit = nullptr, const uint64_t *end_bit = nullptr)
 {
-    Lane &ln = sh.lanes[0];
-    std::lock_guard<std::mutex> lk(ln.mu);
-    HIP_TRY(ctx, hipSetDevice(sh.device));
-    int rc = lane_prepare(ctx, ln);
-    if (rc != PZG_RC_OK) return rc;
-    std::vector<uint64_t> meta(6 * (size_t)n);  // in_off | in_len | out_off | out_cap | dict_off | dict_len, packed layout
-    uint64_t *ioff = meta.data(), *ilen = ioff + n, *ooff = ilen + n, *ocap = ooff + n, *doff = ocap + n, *dlen = doff + n;
+    std::vector<uint8_t> hmeta(96 * (size_t)n), hin, hout;  // the meta block as on the device | the packed input | the packed output
+    LaneCall call(ctx, sh);
+    if (call.rc != PZG_RC_OK) return call.rc;
+    Lane &ln = call.ln;
+    hipStream_t st = call.st;
+    const MetaBlock h(hmeta.data(), n, true);
     size_t ip = 0, op = 0;
     for (uint32_t i = 0; i < n; ++i) {
-        ioff[i] = ip;
-        ilen[i] = b.in_len[i];
+        h.in_off[i] = ip;
+        h.in_len[i] = b.in_len[i];
         ip += pad16(b.in_len[i]);
-        doff[i] = ip;
-        dlen[i] = dict_len[i];
+        h.dict_off[i] = ip;
+        h.dict_len[i] = dict_len[i];
         ip += pad16(dict_len[i]);
-        ooff[i] = op;
-        ocap[i] = b.out_cap[i];
+        h.out_off[i] = op;
+        h.out_cap[i] = b.out_cap[i];
         op += pad16(b.out_cap[i]);
     }
-    std::vector<uint8_t> hin(ip + 16);
+    hin.resize(ip + 16);
     for (uint32_t i = 0; i < n; ++i) {
-        if (ilen[i]) memcpy(hin.data() + ioff[i], b.in_base + b.in_off[i], ilen[i]);
-        if (dlen[i]) memcpy(hin.data() + doff[i], dict_base + dict_off[i], dlen[i]);
+        if (h.in_len[i]) memcpy(hin.data() + h.in_off[i], b.in_base + b.in_off[i], h.in_len[i]);
+        if (h.dict_len[i]) memcpy(hin.data() + h.dict_off[i], dict_base + dict_off[i], h.dict_len[i]);
     }
+    int rc;
     if ((rc = arena_reserve(ctx, ln.d_in[0], ip + 64)) != PZG_RC_OK) return rc;
     if ((rc = arena_reserve(ctx, ln.d_out[0], op + 64)) != PZG_RC_OK) return rc;
     if ((rc = arena_reserve(ctx, ln.d_meta[0], 96 * (size_t)n + 64)) != PZG_RC_OK) return rc;  // (80 n, and a segment's end_bit | start_bit)
-    uint8_t *dm = (uint8_t *)ln.d_meta[0].p;
-    hipStream_t st = ln.s_k;
-    HIP_TRY(ctx, hipMemcpyAsync(dm, meta.data(), 48 * (size_t)n, hipMemcpyHostToDevice, st));
+    const MetaBlock d((uint8_t *)ln.d_meta[0].p, n, true);
+    HIP_TRY(ctx, hipMemcpyAsync(d.in_off, h.in_off, h.extent_bytes, hipMemcpyHostToDevice, st));
     if (start_bit) {
-        HIP_TRY(ctx, hipMemcpyAsync(dm + 80 * (size_t)n, end_bit, 8 * (size_t)n, hipMemcpyHostToDevice, st));
-        HIP_TRY(ctx, hipMemcpyAsync(dm + 88 * (size_t)n, start_bit, (size_t)n, hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemcpyAsync(d.end_bit, end_bit, 8 * (size_t)n, hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemcpyAsync(d.start_bit, start_bit, (size_t)n, hipMemcpyHostToDevice, st));
     }
     HIP_TRY(ctx, hipMemcpyAsync(ln.d_in[0].p, hin.data(), ip, hipMemcpyHostToDevice, st));
-    pzg::InflateArgs a{};
-    a.in_base = (const uint8_t *)ln.d_in[0].p;
-    a.dict_base = a.in_base;
-    a.out_base = (uint8_t *)ln.d_out[0].p;
-    a.in_off = (const uint64_t *)dm;
-    a.in_len = a.in_off + n;
-    a.out_off = a.in_len + n;
-    a.out_cap = a.out_off + n;
-    a.dict_off = a.out_cap + n;
-    a.dict_len = a.dict_off + n;
-    a.out_len = (uint64_t *)(dm + 48 * (size_t)n);
-    a.in_used = a.out_len + n;
-    a.status = (int32_t *)(a.in_used + n);
-    a.adler = (uint32_t *)(a.status + n);
-    a.detail = a.adler + n;
-    a.n = n;
+    pzg::InflateArgs a = inflate_args(d, n, (const uint8_t *)ln.d_in[0].p, (uint8_t *)ln.d_out[0].p, start_bit != nullptr);
     a.counter = ln.d_counter;
     a.raw = raw_mode(b.flags);  // (raw streams: the dictionary is the history, whatever the stream says)
-    if (start_bit) {
-        a.seg = 1u;
-        a.seg_end_bit = (const uint64_t *)(dm + 80 * (size_t)n);
-        a.seg_start_bit = dm + 88 * (size_t)n;
-    }
     strip_for_launch(ctx, ln.d_strip, sh.num_cus, n, 0u, a);
-    HIP_TRY(ctx, hipEventRecord(ln.ev_t0, st));
+    HIP_TRY(ctx, call.begin_timed());
     HIP_TRY(ctx, pzg::launch_inflate(a, ctx->ring_bits, sh.num_cus, st));
-    HIP_TRY(ctx, hipEventRecord(ln.ev_t1, st));
-    std::vector<uint8_t> res(32 * (size_t)n), hout(op + 16);
-    HIP_TRY(ctx, hipMemcpyAsync(res.data(), dm + 48 * (size_t)n, 32 * (size_t)n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, call.end_timed());
+    hout.resize(op + 16);
+    HIP_TRY(ctx, hipMemcpyAsync(h.out_len, d.out_len, 32 * (size_t)n, hipMemcpyDeviceToHost, st));
     if (op) HIP_TRY(ctx, hipMemcpyAsync(hout.data(), ln.d_out[0].p, op, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    {   // the call's kernel span (pzg_last_kernel_ms), as host_path records it
-        float ms = -1.0f;
-        const bool ok = hipEventElapsedTime(&ms, ln.ev_t0, ln.ev_t1) == hipSuccess;
-        std::lock_guard<std::mutex> g(sh.mu);
-        sh.host_ms = ok ? (double)ms : -1.0;
-        sh.last_was_host = true;
-        sh.timed = true;
-    }
-    const uint64_t *olen = (const uint64_t *)res.data(), *used = olen + n;
-    const int32_t *stt = (const int32_t *)(used + n);
-    const uint32_t *ad = (const uint32_t *)(stt + n), *det = ad + n;
+    if ((rc = call.finish()) != PZG_RC_OK) return rc;
     for (uint32_t i = 0; i < n; ++i) {
-        b.out_len[i] = olen[i];
-        b.status[i] = stt[i];
-        if (b.in_used) b.in_used[i] = used[i];
-        if (b.adler) b.adler[i] = ad[i];
-        if (b.detail) {
-            b.detail[2 * (size_t)i] = det[2 * (size_t)i];
-            b.detail[2 * (size_t)i + 1] = det[2 * (size_t)i + 1];
-        }
-        const uint64_t nb = olen[i] < ocap[i] ? olen[i] : ocap[i];
-        if (nb) memcpy(b.out_base + b.out_off[i], hout.data() + ooff[i], nb);
+        store_results(b, i, h, i);
+        const uint64_t nb = std::min(h.out_len[i], h.out_cap[i]);
+        if (nb) memcpy(b.out_base + b.out_off[i], hout.data() + h.out_off[i], nb);
     }
     return PZG_RC_OK;
 }
@@ -1005,22 +1148,20 @@ int pzg_init(int device, pzg_ctx **out)
 {
     if (!out) return PZG_RC_BAD_ARG;
     *out = nullptr;
-    try {
+    return guarded(nullptr, "pzg_init", [&]() -> int {
         int ndev = 0;
         hipError_t e = hipGetDeviceCount(&ndev);
         if (e != hipSuccess || ndev <= 0) return PZG_RC_NO_DEVICE;
         if (device < 0 || device >= ndev) return PZG_RC_BAD_ARG;
         return ctx_create({device}, out);
-    } catch (...) {
-        return PZG_RC_NO_MEMORY;
-    }
+    });
 }
 
 int pzg_init_mask(uint32_t device_mask, pzg_ctx **out)
 {
     if (!out) return PZG_RC_BAD_ARG;
     *out = nullptr;
-    try {
+    return guarded(nullptr, "pzg_init_mask", [&]() -> int {
         int ndev = 0;
         hipError_t e = hipGetDeviceCount(&ndev);
         if (e != hipSuccess || ndev <= 0) return PZG_RC_NO_DEVICE;
@@ -1033,9 +1174,7 @@ int pzg_init_mask(uint32_t device_mask, pzg_ctx **out)
             }
         if (devs.empty()) return PZG_RC_BAD_ARG;
         return ctx_create(devs, out);
-    } catch (...) {
-        return PZG_RC_NO_MEMORY;
-    }
+    });
 }
 
 int pzg_init_devices(const int32_t *devices, uint32_t ndevices, pzg_ctx **out)
@@ -1043,7 +1182,7 @@ int pzg_init_devices(const int32_t *devices, uint32_t ndevices, pzg_ctx **out)
     if (!out) return PZG_RC_BAD_ARG;
     *out = nullptr;
     if (!devices || ndevices == 0 || ndevices > 64u) return PZG_RC_BAD_ARG;
-    try {
+    return guarded(nullptr, "pzg_init_devices", [&]() -> int {
         int ndev = 0;
         hipError_t e = hipGetDeviceCount(&ndev);
         if (e != hipSuccess || ndev <= 0) return PZG_RC_NO_DEVICE;
@@ -1053,9 +1192,7 @@ int pzg_init_devices(const int32_t *devices, uint32_t ndevices, pzg_ctx **out)
             devs.push_back((int)devices[k]);  // (a device may be named more than once: one shard per entry)
         }
         return ctx_create(devs, out);
-    } catch (...) {
-        return PZG_RC_NO_MEMORY;
-    }
+    });
 }
 
 void *pzg_host_alloc(size_t bytes)
@@ -1095,67 +1232,71 @@ void pzg_shutdown(pzg_ctx *ctx)
 int pzg_set_stream(pzg_ctx *ctx, void *hip_stream)
 {
     if (!ctx_live(ctx)) return PZG_RC_BAD_ARG;
-    Shard &sh = *ctx->shards[0];
-    std::lock_guard<std::mutex> g(sh.mu);
-    sh.stream = (hipStream_t)hip_stream;  // NULL = the default (null) stream
-    return PZG_RC_OK;
+    return guarded(ctx, "pzg_set_stream", [&]() -> int {
+        Shard &sh = *ctx->shards[0];
+        std::lock_guard<std::mutex> g(sh.mu);
+        sh.stream = (hipStream_t)hip_stream;  // NULL = the default (null) stream
+        return PZG_RC_OK;
+    });
 }
 
 int pzg_reset_stream(pzg_ctx *ctx)
 {
     if (!ctx_live(ctx)) return PZG_RC_BAD_ARG;
-    Shard &sh = *ctx->shards[0];
-    std::lock_guard<std::mutex> g(sh.mu);
-    sh.stream = sh.own_stream;
-    return PZG_RC_OK;
+    return guarded(ctx, "pzg_reset_stream", [&]() -> int {
+        Shard &sh = *ctx->shards[0];
+        std::lock_guard<std::mutex> g(sh.mu);
+        sh.stream = sh.own_stream;
+        return PZG_RC_OK;
+    });
 }
 
 int pzg_set_option(pzg_ctx *ctx, int option, int64_t value)
 {
     if (!ctx_live(ctx)) return PZG_RC_BAD_ARG;
-    if (option == PZG_OPT_RING_BITS && value >= 11 && value <= 15) {
-        ctx->ring_bits = (int)value;
-        return PZG_RC_OK;
-    }
-    if (option == PZG_OPT_SCRATCH_BYTES && value >= 0) {  // (takes effect launch by launch: an arena larger than its share is given back when next used)
-        ctx->scratch_cap.store((uint64_t)value);
-        return PZG_RC_OK;
-    }
-    if (option == PZG_OPT_PROFILE && (value == 0 || value == 1)) {
-        ctx->profile.store((int)value);
-        return PZG_RC_OK;
-    }
-    if (option == PZG_OPT_BUNDLES && value >= 0 && value <= 2) {
-        ctx->bundles.store((int)value);
-        // (setting it -- to the value it has, too -- makes the next launch look again: a caller that knows its next batches are of
-        // another kind need not wait out the launches a context goes without looking after batches that had nothing for the bundles)
-        for (auto &s : ctx->shards) {
-            std::lock_guard<std::mutex> g(s->mu);
-            s->bundle_skip = 0u;
-            s->bundle_backoff = 0u;
+    return guarded(ctx, "pzg_set_option", [&]() -> int {
+        if (option == PZG_OPT_RING_BITS && value >= 11 && value <= 15) {
+            ctx->ring_bits = (int)value;
+            return PZG_RC_OK;
         }
-        return PZG_RC_OK;
-    }
-    if (option == PZG_OPT_HOST_THREADS && value >= 1 && value <= 256) {  // (not while host-pointer calls are running)
-        try {
+        if (option == PZG_OPT_SCRATCH_BYTES && value >= 0) {  // (takes effect launch by launch: an arena larger than its share is given back when next used)
+            ctx->scratch_cap.store((uint64_t)value);
+            return PZG_RC_OK;
+        }
+        if (option == PZG_OPT_PROFILE && (value == 0 || value == 1)) {
+            ctx->profile.store((int)value);
+            return PZG_RC_OK;
+        }
+        if (option == PZG_OPT_BUNDLES && value >= 0 && value <= 2) {
+            ctx->bundles.store((int)value);
+            // (setting it -- to the value it has, too -- makes the next launch look again: a caller that knows its next batches are of
+            // another kind need not wait out the launches a context goes without looking after batches that had nothing for the bundles)
+            for (auto &s : ctx->shards) {
+                std::lock_guard<std::mutex> g(s->mu);
+                s->bundle_skip = 0u;
+                s->bundle_backoff = 0u;
+            }
+            return PZG_RC_OK;
+        }
+        if (option == PZG_OPT_HOST_THREADS && value >= 1 && value <= 256) {  // (not while host-pointer calls are running)
             ctx->helpers.reset(new Helpers((unsigned)value));
-        } catch (...) {
-            return PZG_RC_NO_MEMORY;
+            return PZG_RC_OK;
         }
-        return PZG_RC_OK;
-    }
-    return PZG_RC_BAD_ARG;
+        return PZG_RC_BAD_ARG;
+    });
 }
 
 int pzg_sync(pzg_ctx *ctx)
 {
     if (!ctx_live(ctx)) return PZG_RC_BAD_ARG;
-    for (auto &s : ctx->shards) {
-        std::lock_guard<std::mutex> g(s->mu);
-        HIP_TRY(ctx, hipSetDevice(s->device));
-        HIP_TRY(ctx, hipStreamSynchronize(s->stream));
-    }
-    return PZG_RC_OK;
+    return guarded(ctx, "pzg_sync", [&]() -> int {
+        for (auto &s : ctx->shards) {
+            std::lock_guard<std::mutex> g(s->mu);
+            HIP_TRY(ctx, hipSetDevice(s->device));
+            HIP_TRY(ctx, hipStreamSynchronize(s->stream));
+        }
+        return PZG_RC_OK;
+    });
 }
 
 int pzg_decompress_many(pzg_ctx *ctx, const uint8_t *in_base, const uint64_t *in_off, const uint64_t *in_len,
@@ -1179,49 +1320,21 @@ int pzg_decompress_many_dict(pzg_ctx *ctx, const uint8_t *in_base, const uint64_
     if (n == 0) return PZG_RC_OK;
     if (!in_base || !in_off || !in_len || !out_off || !out_cap || !out_len || !status) return PZG_RC_BAD_ARG;
     if ((flags & PZG_ASYNC) && !(flags & PZG_DEVICE_PTRS)) return PZG_RC_BAD_ARG;
-    try {
+    const HostBatch b{in_base, in_off, in_len, out_base, out_off, out_cap, out_len, status, detail, in_used, adler, flags};
+    return guarded(ctx, "pzg_decompress_many", [&]() -> int {
         if (flags & PZG_DEVICE_PTRS) {
             if (!out_base || ctx->shards.size() != 1) return PZG_RC_BAD_ARG;  // device pointers belong to ONE device
-            pzg::InflateArgs a{};
-            a.in_base = in_base;
-            a.in_off = in_off;
-            a.in_len = in_len;
-            a.out_base = out_base;
-            a.out_off = out_off;
-            a.out_cap = out_cap;
-            a.out_len = out_len;
-            a.status = status;
-            a.detail = detail;
-            a.in_used = in_used;
-            a.adler = adler;
-            a.n = n;
-            if (with_dict) {
-                a.dict_base = dict_base;
-                a.dict_off = dict_off;
-                a.dict_len = dict_len;
-            }
-            return launch_device(ctx, *ctx->shards[0], a, flags);
+            return launch_device(ctx, *ctx->shards[0], inflate_args(b, n, with_dict ? dict_base : nullptr, dict_off, dict_len), flags);
         }
-        // host pointers: validate the extents (a wrapped offset + length would size an arena far too small)
-        bool any_out = false;
-        for (uint32_t i = 0; i < n; ++i) {
-            if (in_off[i] + in_len[i] < in_off[i] || out_off[i] + out_cap[i] < out_off[i]) return PZG_RC_BAD_ARG;
-            if ((in_len[i] >> 40) || (out_cap[i] >> 40)) return PZG_RC_BAD_ARG;
-            any_out |= out_cap[i] != 0;
-        }
-        if (any_out && !out_base) return PZG_RC_BAD_ARG;
+        if (!extents_ok(b, n)) return PZG_RC_BAD_ARG;
         if (flags & PZG_HOST_PINNED) {  // the copy engines move whole spans of the arenas: extents ascend, none overlaps the next
             if (with_dict) return PZG_RC_BAD_ARG;
             for (uint32_t i = 0; i + 1 < n; ++i)
                 if (in_off[i] + in_len[i] > in_off[i + 1] || out_off[i] + out_cap[i] > out_off[i + 1]) return PZG_RC_BAD_ARG;
         }
-        HostBatch b{in_base, in_off, in_len, out_base, out_off, out_cap, out_len, status, detail, in_used, adler, flags};
         if (with_dict) {
             bool any = false;
-            for (uint32_t i = 0; i < n; ++i) {
-                if (dict_off[i] + dict_len[i] < dict_off[i] || (dict_len[i] >> 32)) return PZG_RC_BAD_ARG;
-                any |= dict_len[i] != 0;
-            }
+            if (!dict_extents_ok(dict_off, dict_len, n, &any)) return PZG_RC_BAD_ARG;
             if (any) return dict_path(ctx, *ctx->shards[0], b, dict_base, dict_off, dict_len, n);
         }
         const size_t S = ctx->shards.size();
@@ -1279,15 +1392,7 @@ int pzg_decompress_many_dict(pzg_ctx *ctx, const uint8_t *in_base, const uint64_
         for (int rc : rcs)
             if (rc != PZG_RC_OK) return rc;
         return PZG_RC_OK;
-    } catch (const std::bad_alloc &) {
-        return PZG_RC_NO_MEMORY;
-    } catch (...) {
-        {
-            std::lock_guard<std::mutex> g(ctx->err_mu);
-            ctx->last_error = "C++ exception inside pzg_decompress_many";
-        }
-        return PZG_RC_HIP_ERROR;
-    }
+    });
 }
 
 int pzg_decompress_many_segments(pzg_ctx *ctx, const uint8_t *in_base, const uint64_t *in_off, const uint64_t *in_len,
@@ -1304,44 +1409,17 @@ int pzg_decompress_many_segments(pzg_ctx *ctx, const uint8_t *in_base, const uin
     if (n == 0) return PZG_RC_OK;
     if (!in_base || !in_off || !in_len || !start_bit || !end_bit || !out_off || !out_cap || !out_len || !status) return PZG_RC_BAD_ARG;
     if (!dict_base || !dict_off || !dict_len) return PZG_RC_BAD_ARG;
-    try {
+    const HostBatch b{in_base, in_off, in_len, out_base, out_off, out_cap, out_len, status, detail, in_used, adler, flags};
+    return guarded(ctx, "pzg_decompress_many_segments", [&]() -> int {
         if (flags & PZG_DEVICE_PTRS) {
             if (!out_base) return PZG_RC_BAD_ARG;
-            pzg::InflateArgs a{};
-            a.in_base = in_base;
-            a.in_off = in_off;
-            a.in_len = in_len;
-            a.out_base = out_base;
-            a.out_off = out_off;
-            a.out_cap = out_cap;
-            a.out_len = out_len;
-            a.status = status;
-            a.detail = detail;
-            a.in_used = in_used;
-            a.adler = adler;
-            a.n = n;
-            a.dict_base = dict_base;
-            a.dict_off = dict_off;
-            a.dict_len = dict_len;
-            a.seg = 1u;
-            a.seg_start_bit = start_bit;
-            a.seg_end_bit = end_bit;
-            return launch_device(ctx, *ctx->shards[0], a, flags);
+            return launch_device(ctx, *ctx->shards[0], inflate_args(b, n, dict_base, dict_off, dict_len, start_bit, end_bit), flags);
         }
-        bool any_out = false;
-        for (uint32_t i = 0; i < n; ++i) {
-            if (in_off[i] + in_len[i] < in_off[i] || out_off[i] + out_cap[i] < out_off[i]) return PZG_RC_BAD_ARG;
-            if ((in_len[i] >> 40) || (out_cap[i] >> 40)) return PZG_RC_BAD_ARG;
-            if (dict_off[i] + dict_len[i] < dict_off[i] || (dict_len[i] >> 32)) return PZG_RC_BAD_ARG;
+        if (!extents_ok(b, n) || !dict_extents_ok(dict_off, dict_len, n)) return PZG_RC_BAD_ARG;
+        for (uint32_t i = 0; i < n; ++i)
             if (start_bit[i] > 7u || end_bit[i] > 8u * in_len[i]) return PZG_RC_BAD_ARG;
-            any_out |= out_cap[i] != 0;
-        }
-        if (any_out && !out_base) return PZG_RC_BAD_ARG;
-        HostBatch b{in_base, in_off, in_len, out_base, out_off, out_cap, out_len, status, detail, in_used, adler, flags};
         return dict_path(ctx, *ctx->shards[0], b, dict_base, dict_off, dict_len, n, start_bit, end_bit);
-    } catch (const std::bad_alloc &) {
-        return PZG_RC_NO_MEMORY;
-    }
+    });
 }
 
 int pzg_index_build(pzg_ctx *ctx, const uint8_t *in, uint64_t in_len, uint8_t *out, uint64_t out_cap, uint64_t span, pzg_index_point *points,
@@ -1355,46 +1433,32 @@ int pzg_index_build(pzg_ctx *ctx, const uint8_t *in, uint64_t in_len, uint8_t *o
     if ((in_len >> 34) || (out_cap >> 40)) return PZG_RC_BAD_ARG;
     if (span == 0) span = 1ull << 20;
     const bool dev = (flags & PZG_DEVICE_PTRS) != 0;
-    Shard &sh = *ctx->shards[0];
-    Lane &ln = sh.lanes[0];
-    try {
-        std::lock_guard<std::mutex> lk(ln.mu);
-        HIP_TRY(ctx, hipSetDevice(sh.device));
-        int rc = lane_prepare(ctx, ln);
-        if (rc != PZG_RC_OK) return rc;
-        hipStream_t st = ln.s_k;
+    return guarded(ctx, "pzg_index_build", [&]() -> int {
+        Shard &sh = *ctx->shards[0];
+        LaneCall call(ctx, sh);
+        if (call.rc != PZG_RC_OK) return call.rc;
+        Lane &ln = call.ln;
+        hipStream_t st = call.st;
         // device side: the input, then out | points | windows in one arena (host pointers), and 128 bytes of arguments and results
-        const uint8_t *d_in = in;
+        const uint8_t *d_in = nullptr;
         uint8_t *d_out = out, *d_win = windows;
         uint64_t *d_pts = (uint64_t *)points;
         const size_t pts_off = pad256(out_cap), win_off = pts_off + pad256(16 * (size_t)max_points);
+        int rc;
         if (!dev) {
-            if ((rc = arena_reserve(ctx, ln.d_in[0], in_len + 64)) != PZG_RC_OK) return rc;
             if ((rc = arena_reserve(ctx, ln.d_out[0], win_off + (windows ? 32768 * (size_t)max_points : 0) + 64)) != PZG_RC_OK) return rc;
-            d_in = (const uint8_t *)ln.d_in[0].p;
             d_out = (uint8_t *)ln.d_out[0].p;
             d_pts = (uint64_t *)(d_out + pts_off);
             d_win = windows ? d_out + win_off : nullptr;
-            if (in_len) HIP_TRY(ctx, hipMemcpyAsync(ln.d_in[0].p, in, in_len, hipMemcpyHostToDevice, st));
         }
+        if ((rc = stage_input(call, in, in_len, dev, d_in)) != PZG_RC_OK) return rc;
         if ((rc = arena_reserve(ctx, ln.d_meta[0], 256)) != PZG_RC_OK) return rc;
         uint8_t *dm = (uint8_t *)ln.d_meta[0].p;
-        // [0] in_off [1] in_len [2] out_off [3] out_cap | [4] out_len [5] in_used | words: status, adler, detail0, detail1, points
+        // a meta block of one stream (64 bytes: hm[4] out_len, hm[5] in_used, then the words status, adler, detail0, detail1), and
+        // behind it the number of points; at 128, a slot for the kernel when the caller wants no points
         uint64_t hm[8] = {0, in_len, 0, out_cap, 0, 0, 0, 0};
         HIP_TRY(ctx, hipMemcpyAsync(dm, hm, sizeof(hm), hipMemcpyHostToDevice, st));
-        pzg::InflateArgs a{};
-        a.in_base = d_in;
-        a.out_base = d_out;
-        a.in_off = (const uint64_t *)dm;
-        a.in_len = a.in_off + 1;
-        a.out_off = a.in_off + 2;
-        a.out_cap = a.in_off + 3;
-        a.out_len = (uint64_t *)dm + 4;
-        a.in_used = (uint64_t *)dm + 5;
-        a.status = (int32_t *)(dm + 48);
-        a.adler = (uint32_t *)(dm + 52);
-        a.detail = (uint32_t *)(dm + 56);
-        a.n = 1;
+        pzg::InflateArgs a = inflate_args(MetaBlock(dm, 1, false), 1, d_in, d_out);
         a.counter = ln.d_counter;
         a.raw = 1u;
         a.seg = 1u;
@@ -1406,14 +1470,14 @@ int pzg_index_build(pzg_ctx *ctx, const uint8_t *in, uint64_t in_len, uint8_t *o
             a.idx_points = (uint64_t *)(dm + 128);
             a.idx_cap = 0;
         }
-        HIP_TRY(ctx, hipEventRecord(ln.ev_t0, st));
+        HIP_TRY(ctx, call.begin_timed());
         HIP_TRY(ctx, pzg::launch_inflate(a, 15, sh.num_cus, st));
         HIP_TRY(ctx, pzg::launch_index_windows(d_out, a.out_cap, a.idx_points, a.idx_count, a.idx_cap, a.status, d_win, st));
-        HIP_TRY(ctx, hipEventRecord(ln.ev_t1, st));
+        HIP_TRY(ctx, call.end_timed());
         HIP_TRY(ctx, hipMemcpyAsync(hm, dm, sizeof(hm), hipMemcpyDeviceToHost, st));
         uint32_t cnt = 0;
         HIP_TRY(ctx, hipMemcpyAsync(&cnt, dm + 64, 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipStreamSynchronize(st));
+        if ((rc = call.finish()) != PZG_RC_OK) return rc;
         uint32_t w[4];
         memcpy(w, &hm[6], 16);
         *out_len = hm[4];
@@ -1430,29 +1494,10 @@ int pzg_index_build(pzg_ctx *ctx, const uint8_t *in, uint64_t in_len, uint8_t *o
             const size_t np = cnt < max_points ? cnt : max_points;
             if (nb) HIP_TRY(ctx, hipMemcpy(out, d_out, nb, hipMemcpyDeviceToHost));
             if (np) HIP_TRY(ctx, hipMemcpy(points, d_pts, 16 * np, hipMemcpyDeviceToHost));
-            if (np && windows && w[0] == 0u) {
-                // (a point below 32768 has a shorter window, at the end of its slot: the front of the caller's slot stays as it is.
-                // out_pos ascends, so these are the first few points; whole slots follow in one copy)
-                size_t k = 0;
-                for (; k < np && points[k].out_pos < 32768u; ++k) {
-                    const size_t at = 32768u * k + (32768u - (size_t)points[k].out_pos);
-                    HIP_TRY(ctx, hipMemcpy(windows + at, d_win + at, (size_t)points[k].out_pos, hipMemcpyDeviceToHost));
-                }
-                if (k < np) HIP_TRY(ctx, hipMemcpy(windows + 32768u * k, d_win + 32768u * k, 32768u * (np - k), hipMemcpyDeviceToHost));
-            }
-        }
-        {
-            float ms = -1.0f;
-            const bool ok = hipEventElapsedTime(&ms, ln.ev_t0, ln.ev_t1) == hipSuccess;
-            std::lock_guard<std::mutex> g(sh.mu);
-            sh.host_ms = ok ? (double)ms : -1.0;
-            sh.last_was_host = true;
-            sh.timed = true;
+            if (np && windows && w[0] == 0u) return copy_back_windows(ctx, points, np, windows, d_win);
         }
         return PZG_RC_OK;
-    } catch (const std::bad_alloc &) {
-        return PZG_RC_NO_MEMORY;
-    }
+    });
 }
 
 int pzg_index_scan(pzg_ctx *ctx, const uint8_t *in, uint64_t in_len, uint64_t chunk, uint64_t span, pzg_index_point *points, uint32_t max_points,
@@ -1468,41 +1513,26 @@ int pzg_index_scan(pzg_ctx *ctx, const uint8_t *in, uint64_t in_len, uint64_t ch
     if (span == 0) span = 1ull << 20;
     const uint64_t nchunks64 = in_len ? (in_len + chunk - 1u) / chunk : 1u;
     const bool dev = (flags & PZG_DEVICE_PTRS) != 0;
-    Shard &sh = *ctx->shards[0];
-    Lane &ln = sh.lanes[0];
-    // the call's own scratch, freed whatever way the call ends
-    struct Scratch {
-        void *p = nullptr;
-        ~Scratch()
-        {
-            if (p) (void)hipFree(p);
-        }
-    } scratch;
-    try {
-        std::lock_guard<std::mutex> lk(ln.mu);
-        HIP_TRY(ctx, hipSetDevice(sh.device));
-        int rc = lane_prepare(ctx, ln);
-        if (rc != PZG_RC_OK) return rc;
-        hipStream_t st = ln.s_k;
-        const uint8_t *d_in = in;
+    return guarded(ctx, "pzg_index_scan", [&]() -> int {
+        Shard &sh = *ctx->shards[0];
+        CallScratch scratch;
+        LaneCall call(ctx, sh);
+        if (call.rc != PZG_RC_OK) return call.rc;
+        Lane &ln = call.ln;
+        hipStream_t st = call.st;
+        const uint8_t *d_in = nullptr;
         uint8_t *d_win = windows;
         uint64_t *d_pts = (uint64_t *)points;
         const size_t win_off = pad256(16 * (size_t)max_points);
+        int rc;
         if (!dev) {
-            if ((rc = arena_reserve(ctx, ln.d_in[0], in_len + 64)) != PZG_RC_OK) return rc;
             if ((rc = arena_reserve(ctx, ln.d_out[0], win_off + (windows ? 32768 * (size_t)max_points : 0) + 64)) != PZG_RC_OK) return rc;
-            d_in = (const uint8_t *)ln.d_in[0].p;
             d_pts = (uint64_t *)ln.d_out[0].p;
             d_win = windows ? (uint8_t *)ln.d_out[0].p + win_off : nullptr;
-            if (in_len) HIP_TRY(ctx, hipMemcpyAsync(ln.d_in[0].p, in, in_len, hipMemcpyHostToDevice, st));
         }
+        if ((rc = stage_input(call, in, in_len, dev, d_in)) != PZG_RC_OK) return rc;
         if ((rc = arena_reserve(ctx, ln.d_meta[0], 256)) != PZG_RC_OK) return rc;
-        const size_t need = pzg::scan_scratch_bytes((uint32_t)nchunks64);
-        if (hipMalloc(&scratch.p, need) != hipSuccess) {
-            (void)hipGetLastError();
-            scratch.p = nullptr;
-            return PZG_RC_NO_MEMORY;
-        }
+        if ((rc = scratch.reserve(pzg::scan_scratch_bytes((uint32_t)nchunks64))) != PZG_RC_OK) return rc;
         pzg::ScanArgs a{};
         a.in = d_in;
         a.in_len = in_len;
@@ -1513,16 +1543,16 @@ int pzg_index_scan(pzg_ctx *ctx, const uint8_t *in, uint64_t in_len, uint64_t ch
         a.points = d_pts;
         a.windows = d_win;
         a.result = (pzg::ScanResult *)ln.d_meta[0].p;
-        HIP_TRY(ctx, hipEventRecord(ln.ev_t0, st));
+        HIP_TRY(ctx, call.begin_timed());
         HIP_TRY(ctx, pzg::launch_scan(a, (uint8_t *)scratch.p, st));
-        HIP_TRY(ctx, hipEventRecord(ln.ev_t1, st));
+        HIP_TRY(ctx, call.end_timed());
         struct {
             int32_t status;
             uint32_t d0, d1, npoints;
             uint64_t out_len, in_used;
         } r{};
         HIP_TRY(ctx, hipMemcpyAsync(&r, ln.d_meta[0].p, sizeof(r), hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipStreamSynchronize(st));
+        if ((rc = call.finish()) != PZG_RC_OK) return rc;
         *out_len = r.out_len;
         *status = r.status;
         if (in_used) *in_used = r.in_used;
@@ -1534,58 +1564,11 @@ int pzg_index_scan(pzg_ctx *ctx, const uint8_t *in, uint64_t in_len, uint64_t ch
         if (!dev && r.status == 0) {
             const size_t np = r.npoints < max_points ? r.npoints : max_points;
             if (np) HIP_TRY(ctx, hipMemcpy(points, d_pts, 16 * np, hipMemcpyDeviceToHost));
-            if (np && windows) {  // (as pzg_index_build: the front of a short window's slot stays the caller's)
-                size_t k = 0;
-                for (; k < np && points[k].out_pos < 32768u; ++k) {
-                    const size_t at = 32768u * k + (32768u - (size_t)points[k].out_pos);
-                    HIP_TRY(ctx, hipMemcpy(windows + at, d_win + at, (size_t)points[k].out_pos, hipMemcpyDeviceToHost));
-                }
-                if (k < np) HIP_TRY(ctx, hipMemcpy(windows + 32768u * k, d_win + 32768u * k, 32768u * (np - k), hipMemcpyDeviceToHost));
-            }
-        }
-        {
-            float ms = -1.0f;
-            const bool ok = hipEventElapsedTime(&ms, ln.ev_t0, ln.ev_t1) == hipSuccess;
-            std::lock_guard<std::mutex> g(sh.mu);
-            sh.host_ms = ok ? (double)ms : -1.0;
-            sh.last_was_host = true;
-            sh.timed = true;
+            if (np && windows) return copy_back_windows(ctx, points, np, windows, d_win);
         }
         return PZG_RC_OK;
-    } catch (const std::bad_alloc &) {
-        return PZG_RC_NO_MEMORY;
-    }
+    });
 }
-
-namespace {
-// scratch of one call, freed whatever way the call ends
-struct CallScratch {
-    void *p = nullptr;
-    ~CallScratch()
-    {
-        if (p) (void)hipFree(p);
-    }
-    int reserve(size_t bytes)
-    {
-        if (hipMalloc(&p, bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            p = nullptr;
-            return PZG_RC_NO_MEMORY;
-        }
-        return PZG_RC_OK;
-    }
-};
-
-void lane_timed(Shard &sh, Lane &ln)
-{
-    float ms = -1.0f;
-    const bool ok = hipEventElapsedTime(&ms, ln.ev_t0, ln.ev_t1) == hipSuccess;
-    std::lock_guard<std::mutex> g(sh.mu);
-    sh.host_ms = ok ? (double)ms : -1.0;
-    sh.last_was_host = true;
-    sh.timed = true;
-}
-}  // namespace
 
 int pzg_gzip_find_members(pzg_ctx *ctx, const uint8_t *in, uint64_t in_len, uint64_t chunk, uint64_t *starts, uint32_t *bsize, uint32_t max_members,
                           uint32_t *nmembers, uint32_t flags)
@@ -1599,27 +1582,23 @@ int pzg_gzip_find_members(pzg_ctx *ctx, const uint8_t *in, uint64_t in_len, uint
     if (chunk < 64u) return PZG_RC_BAD_ARG;
     const uint64_t nchunks = in_len ? (in_len + chunk - 1u) / chunk : 1u;
     const bool dev = (flags & PZG_DEVICE_PTRS) != 0;
-    Shard &sh = *ctx->shards[0];
-    Lane &ln = sh.lanes[0];
-    CallScratch scratch;
-    try {
-        std::lock_guard<std::mutex> lk(ln.mu);
-        HIP_TRY(ctx, hipSetDevice(sh.device));
-        int rc = lane_prepare(ctx, ln);
-        if (rc != PZG_RC_OK) return rc;
-        hipStream_t st = ln.s_k;
-        const uint8_t *d_in = in;
+    return guarded(ctx, "pzg_gzip_find_members", [&]() -> int {
+        CallScratch scratch;
+        LaneCall call(ctx, *ctx->shards[0]);
+        if (call.rc != PZG_RC_OK) return call.rc;
+        Lane &ln = call.ln;
+        hipStream_t st = call.st;
+        const uint8_t *d_in = nullptr;
         uint64_t *d_starts = starts;
         uint32_t *d_bsize = bsize;
+        int rc;
         if (!dev) {
             const size_t bs_off = pad256(8 * (size_t)max_members);
-            if ((rc = arena_reserve(ctx, ln.d_in[0], in_len + 64)) != PZG_RC_OK) return rc;
             if ((rc = arena_reserve(ctx, ln.d_out[0], bs_off + 4 * (size_t)max_members + 64)) != PZG_RC_OK) return rc;
-            d_in = (const uint8_t *)ln.d_in[0].p;
             d_starts = (uint64_t *)ln.d_out[0].p;
             d_bsize = (uint32_t *)((uint8_t *)ln.d_out[0].p + bs_off);
-            if (in_len) HIP_TRY(ctx, hipMemcpyAsync(ln.d_in[0].p, in, in_len, hipMemcpyHostToDevice, st));
         }
+        if ((rc = stage_input(call, in, in_len, dev, d_in)) != PZG_RC_OK) return rc;
         if ((rc = scratch.reserve(pzg::members_find_scratch_bytes(nchunks))) != PZG_RC_OK) return rc;
         pzg::MemberArgs a{};
         a.in = d_in;
@@ -1629,23 +1608,20 @@ int pzg_gzip_find_members(pzg_ctx *ctx, const uint8_t *in, uint64_t in_len, uint
         a.starts = d_starts;
         a.bsize = d_bsize;
         a.max_members = max_members;
-        HIP_TRY(ctx, hipEventRecord(ln.ev_t0, st));
+        HIP_TRY(ctx, call.begin_timed());
         HIP_TRY(ctx, pzg::launch_members_find(a, (uint8_t *)scratch.p, st));
-        HIP_TRY(ctx, hipEventRecord(ln.ev_t1, st));
+        HIP_TRY(ctx, call.end_timed());
         uint64_t total = 0;
         HIP_TRY(ctx, hipMemcpyAsync(&total, pzg::members_find_total(nchunks, (const uint8_t *)scratch.p), 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipStreamSynchronize(st));
+        if ((rc = call.finish()) != PZG_RC_OK) return rc;
         *nmembers = total > 0xffffffffull ? 0xffffffffu : (uint32_t)total;
         if (!dev) {
             const size_t n = total < max_members ? (size_t)total : max_members;
             if (n) HIP_TRY(ctx, hipMemcpy(starts, d_starts, 8 * n, hipMemcpyDeviceToHost));
             if (n) HIP_TRY(ctx, hipMemcpy(bsize, d_bsize, 4 * n, hipMemcpyDeviceToHost));
         }
-        lane_timed(sh, ln);
         return PZG_RC_OK;
-    } catch (const std::bad_alloc &) {
-        return PZG_RC_NO_MEMORY;
-    }
+    });
 }
 
 int pzg_gzip_layout(pzg_ctx *ctx, const uint8_t *in, uint64_t in_len, const uint64_t *starts, uint32_t m, uint64_t out_base_off, uint64_t *in_off,
@@ -1660,17 +1636,13 @@ int pzg_gzip_layout(pzg_ctx *ctx, const uint8_t *in, uint64_t in_len, const uint
     if (!dev)
         for (uint32_t j = 0; j < m; ++j)
             if (starts[j] > in_len || (j && starts[j] < starts[j - 1])) return PZG_RC_BAD_ARG;
-    Shard &sh = *ctx->shards[0];
-    Lane &ln = sh.lanes[0];
-    CallScratch scratch;
-    try {
-        std::lock_guard<std::mutex> lk(ln.mu);
-        HIP_TRY(ctx, hipSetDevice(sh.device));
-        int rc = lane_prepare(ctx, ln);
-        if (rc != PZG_RC_OK) return rc;
-        hipStream_t st = ln.s_k;
+    return guarded(ctx, "pzg_gzip_layout", [&]() -> int {
+        CallScratch scratch;
+        LaneCall call(ctx, *ctx->shards[0]);
+        if (call.rc != PZG_RC_OK) return call.rc;
+        Lane &ln = call.ln;
+        hipStream_t st = call.st;
         pzg::LayoutArgs a{};
-        a.in = in;
         a.in_len = in_len;
         a.m = m;
         a.out_base_off = out_base_off;
@@ -1680,36 +1652,33 @@ int pzg_gzip_layout(pzg_ctx *ctx, const uint8_t *in, uint64_t in_len, const uint
         a.out_off = out_off;
         a.out_cap = out_cap;
         const size_t row = pad256(8 * (size_t)m);
+        uint8_t *d = nullptr;  // host pointers: the four result rows and the starts, in the lane's output arena
+        int rc;
         if (!dev) {
-            if ((rc = arena_reserve(ctx, ln.d_in[0], in_len + 64)) != PZG_RC_OK) return rc;
             if ((rc = arena_reserve(ctx, ln.d_out[0], 5 * row)) != PZG_RC_OK) return rc;
-            uint8_t *d = (uint8_t *)ln.d_out[0].p;
-            a.in = (const uint8_t *)ln.d_in[0].p;
+            d = (uint8_t *)ln.d_out[0].p;
             a.starts = (const uint64_t *)(d + 4 * row);
             a.in_off = (uint64_t *)d;
             a.in_lenv = (uint64_t *)(d + row);
             a.out_off = (uint64_t *)(d + 2 * row);
             a.out_cap = (uint64_t *)(d + 3 * row);
-            if (in_len) HIP_TRY(ctx, hipMemcpyAsync(ln.d_in[0].p, in, in_len, hipMemcpyHostToDevice, st));
-            HIP_TRY(ctx, hipMemcpyAsync(d + 4 * row, starts, 8 * (size_t)m, hipMemcpyHostToDevice, st));
         }
+        if ((rc = stage_input(call, in, in_len, dev, a.in)) != PZG_RC_OK) return rc;
+        if (!dev) HIP_TRY(ctx, hipMemcpyAsync(d + 4 * row, starts, 8 * (size_t)m, hipMemcpyHostToDevice, st));
         if ((rc = scratch.reserve(pzg::members_layout_scratch_bytes(m))) != PZG_RC_OK) return rc;
-        HIP_TRY(ctx, hipEventRecord(ln.ev_t0, st));
+        HIP_TRY(ctx, call.begin_timed());
         HIP_TRY(ctx, pzg::launch_members_layout(a, (uint8_t *)scratch.p, st));
-        HIP_TRY(ctx, hipEventRecord(ln.ev_t1, st));
+        HIP_TRY(ctx, call.end_timed());
         uint64_t sum = 0;
         HIP_TRY(ctx, hipMemcpyAsync(&sum, pzg::members_layout_total(m, (const uint8_t *)scratch.p), 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipStreamSynchronize(st));
+        if ((rc = call.finish()) != PZG_RC_OK) return rc;
         *total = sum;
         if (!dev) {
             uint64_t *const host[4] = {in_off, in_lenv, out_off, out_cap};
-            for (int k = 0; k < 4; ++k) HIP_TRY(ctx, hipMemcpy(host[k], (uint8_t *)ln.d_out[0].p + k * row, 8 * (size_t)m, hipMemcpyDeviceToHost));
+            for (int k = 0; k < 4; ++k) HIP_TRY(ctx, hipMemcpy(host[k], d + k * row, 8 * (size_t)m, hipMemcpyDeviceToHost));
         }
-        lane_timed(sh, ln);
         return PZG_RC_OK;
-    } catch (const std::bad_alloc &) {
-        return PZG_RC_NO_MEMORY;
-    }
+    });
 }
 
 int pzg_decompress_many_sharded(pzg_ctx *ctx, const pzg_device_batch *batches, uint32_t nbatches, uint32_t flags)
@@ -1723,26 +1692,14 @@ int pzg_decompress_many_sharded(pzg_ctx *ctx, const pzg_device_batch *batches, u
         if (q.n && (!q.in_base || !q.in_off || !q.in_len || !q.out_base || !q.out_off || !q.out_cap || !q.out_len || !q.status))
             return PZG_RC_BAD_ARG;
     }
-    try {
+    return guarded(ctx, "pzg_decompress_many_sharded", [&]() -> int {
         // every batch enqueued on its own device's stream first (launches are asynchronous: one host thread feeds them all) ...
         int rc = PZG_RC_OK;
         for (uint32_t b = 0; b < nbatches && rc == PZG_RC_OK; ++b) {
             const pzg_device_batch &q = batches[b];
             if (q.n == 0) continue;
-            pzg::InflateArgs a{};
-            a.in_base = q.in_base;
-            a.in_off = q.in_off;
-            a.in_len = q.in_len;
-            a.out_base = q.out_base;
-            a.out_off = q.out_off;
-            a.out_cap = q.out_cap;
-            a.out_len = q.out_len;
-            a.status = q.status;
-            a.detail = q.detail;
-            a.in_used = q.in_used;
-            a.adler = q.adler;
-            a.n = q.n;
-            rc = launch_device(ctx, *ctx->shards[q.shard], a, (flags & (PZG_GZIP | PZG_LPT_ORDER | PZG_RAW | PZG_CRC32)) | PZG_DEVICE_PTRS | PZG_ASYNC);
+            const HostBatch hb{q.in_base, q.in_off, q.in_len, q.out_base, q.out_off, q.out_cap, q.out_len, q.status, q.detail, q.in_used, q.adler, flags};
+            rc = launch_device(ctx, *ctx->shards[q.shard], inflate_args(hb, q.n), (flags & (PZG_GZIP | PZG_LPT_ORDER | PZG_RAW | PZG_CRC32)) | PZG_DEVICE_PTRS | PZG_ASYNC);
         }
         // ... then waited for, unless the caller does that (on an error too: nothing enqueued may outlive a failed call)
         if (!(flags & PZG_ASYNC) || rc != PZG_RC_OK) {
@@ -1753,9 +1710,7 @@ int pzg_decompress_many_sharded(pzg_ctx *ctx, const pzg_device_batch *batches, u
             }
         }
         return rc;
-    } catch (...) {
-        return PZG_RC_NO_MEMORY;
-    }
+    });
 }
 
 // ---- resumable decoders (decompressIncremental) ---------------------------------------------------------------------
@@ -1809,9 +1764,11 @@ extern "C" {
 int pzg_decoder_last_feed_ms(pzg_decoder *dec, double out[5])
 {
     if (!dec || !out) return PZG_RC_BAD_ARG;
-    std::lock_guard<std::mutex> g(dec->mu);
-    for (int k = 0; k < 5; ++k) out[k] = dec->last_feed[k];
-    return PZG_RC_OK;
+    return guarded(dec->ctx, "pzg_decoder_last_feed_ms", [&]() -> int {
+        std::lock_guard<std::mutex> g(dec->mu);
+        for (int k = 0; k < 5; ++k) out[k] = dec->last_feed[k];
+        return PZG_RC_OK;
+    });
 }
 
 int pzg_decoder_create(pzg_ctx *ctx, uint32_t n, pzg_decoder **out)
@@ -1819,7 +1776,7 @@ int pzg_decoder_create(pzg_ctx *ctx, uint32_t n, pzg_decoder **out)
     if (out) *out = nullptr;
     if (!ctx_live(ctx) || !out || n == 0 || ctx->shards.size() != 1) return PZG_RC_BAD_ARG;
     pzg_decoder *d = nullptr;
-    try {
+    const int rc = guarded(ctx, "pzg_decoder_create", [&]() -> int {
         Shard &sh = *ctx->shards[0];
         HIP_TRY(ctx, hipSetDevice(sh.device));
         d = new pzg_decoder();
@@ -1828,27 +1785,18 @@ int pzg_decoder_create(pzg_ctx *ctx, uint32_t n, pzg_decoder **out)
         d->device = sh.device;
         d->n = n;
         d->stride = pzg::resume_state_bytes();
-        // every failure from here on leaves through pzg_decoder_destroy: nothing allocated so far is leaked
-        int rc = PZG_RC_OK;
         hipError_t e;
         if (hipMalloc((void **)&d->d_state, d->stride * (size_t)n) != hipSuccess || hipMalloc((void **)&d->d_counter, 256) != hipSuccess)
-            rc = PZG_RC_NO_MEMORY;
-        else if ((e = hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking)) != hipSuccess)
-            rc = hip_fail(ctx, e, "hipStreamCreateWithFlags");
-        else if ((e = hipMemsetAsync(d->d_state, 0, d->stride * (size_t)n, d->stream)) != hipSuccess)
-            rc = hip_fail(ctx, e, "hipMemsetAsync");
-        else if ((e = hipStreamSynchronize(d->stream)) != hipSuccess)
-            rc = hip_fail(ctx, e, "hipStreamSynchronize");
-        if (rc != PZG_RC_OK) {
-            pzg_decoder_destroy(d);
-            return rc;
-        }
-        *out = d;
+            return PZG_RC_NO_MEMORY;
+        if ((e = hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking)) != hipSuccess) return hip_fail(ctx, e, "hipStreamCreateWithFlags");
+        if ((e = hipMemsetAsync(d->d_state, 0, d->stride * (size_t)n, d->stream)) != hipSuccess) return hip_fail(ctx, e, "hipMemsetAsync");
+        if ((e = hipStreamSynchronize(d->stream)) != hipSuccess) return hip_fail(ctx, e, "hipStreamSynchronize");
         return PZG_RC_OK;
-    } catch (...) {
-        if (d) pzg_decoder_destroy(d);
-        return PZG_RC_NO_MEMORY;
-    }
+    });
+    // every failure leaves through pzg_decoder_destroy: nothing allocated so far is leaked
+    if (rc != PZG_RC_OK && d) pzg_decoder_destroy(d);
+    if (rc == PZG_RC_OK) *out = d;
+    return rc;
 }
 
 void pzg_decoder_destroy(pzg_decoder *dec)
@@ -1881,18 +1829,20 @@ int pzg_decoder_reset(pzg_decoder *dec, const uint32_t *idx, uint32_t m)
 {
     if (!dec) return PZG_RC_BAD_ARG;
     pzg_ctx *ctx = dec->ctx;
-    std::lock_guard<std::mutex> g(dec->mu);
-    HIP_TRY(ctx, hipSetDevice(dec->device));
-    if (!idx) {
-        HIP_TRY(ctx, hipMemsetAsync(dec->d_state, 0, dec->stride * (size_t)dec->n, dec->stream));
-    } else {
-        for (uint32_t j = 0; j < m; ++j) {
-            if (idx[j] >= dec->n) return PZG_RC_BAD_ARG;
-            HIP_TRY(ctx, hipMemsetAsync(dec->d_state + dec->stride * (size_t)idx[j], 0, pzg::resume_scalar_bytes(), dec->stream));
+    return guarded(ctx, "pzg_decoder_reset", [&]() -> int {
+        std::lock_guard<std::mutex> g(dec->mu);
+        HIP_TRY(ctx, hipSetDevice(dec->device));
+        if (!idx) {
+            HIP_TRY(ctx, hipMemsetAsync(dec->d_state, 0, dec->stride * (size_t)dec->n, dec->stream));
+        } else {
+            for (uint32_t j = 0; j < m; ++j) {
+                if (idx[j] >= dec->n) return PZG_RC_BAD_ARG;
+                HIP_TRY(ctx, hipMemsetAsync(dec->d_state + dec->stride * (size_t)idx[j], 0, pzg::resume_scalar_bytes(), dec->stream));
+            }
         }
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(dec->stream));
-    return PZG_RC_OK;
+        HIP_TRY(ctx, hipStreamSynchronize(dec->stream));
+        return PZG_RC_OK;
+    });
 }
 
 int pzg_decoder_feed(pzg_decoder *dec, const uint32_t *idx, uint32_t m, const uint8_t *in_base, const uint64_t *in_off, const uint64_t *in_len,
@@ -1904,7 +1854,7 @@ int pzg_decoder_feed(pzg_decoder *dec, const uint32_t *idx, uint32_t m, const ui
     pzg_ctx *ctx = dec->ctx;
     if (!idx) m = dec->n;
     if (m == 0) return PZG_RC_OK;
-    try {
+    return guarded(ctx, "pzg_decoder_feed", [&]() -> int {
         for (uint32_t j = 0; j < m; ++j) {
             if (idx && idx[j] >= dec->n) return PZG_RC_BAD_ARG;
             if (out_cap[j] < 4096u || (out_cap[j] >> 40) || (in_len[j] >> 40)) return PZG_RC_BAD_ARG;
@@ -2087,15 +2037,8 @@ int pzg_decoder_feed(pzg_decoder *dec, const uint32_t *idx, uint32_t m, const ui
             }
             hipError_t herr = hipSuccess;
             const char *hwhat = "";
-#define FEED_TRY(call)                              \
-    do {                                            \
-        if (herr == hipSuccess) {                   \
-            herr = (call);                          \
-            if (herr != hipSuccess) hwhat = #call;  \
-        }                                           \
-    } while (0)
-            FEED_TRY(hipMemcpyAsync(dm, dec->h_meta.p, 32 * (size_t)m, hipMemcpyHostToDevice, dec->s_up));
-            FEED_TRY(hipMemcpyAsync(dm + 68 * (size_t)m, h_final, m, hipMemcpyHostToDevice, dec->s_up));
+            PIPE_TRY(hipMemcpyAsync(dm, dec->h_meta.p, 32 * (size_t)m, hipMemcpyHostToDevice, dec->s_up));
+            PIPE_TRY(hipMemcpyAsync(dm + 68 * (size_t)m, h_final, m, hipMemcpyHostToDevice, dec->s_up));
             std::mutex pm;
             std::condition_variable pcv;
             uint32_t issued = 0, fetched = 0;
@@ -2220,29 +2163,29 @@ int pzg_decoder_feed(pzg_decoder *dec, const uint32_t *idx, uint32_t m, const ui
                             if (ilen[j]) memcpy(hin + ioff[j], in_base + in_off[j], ilen[j]);
                     });
                     t_pack += ms_since(tp0);
-                    if (ib) FEED_TRY(hipMemcpyAsync((uint8_t *)dec->d_in.p + ioff[j0], hin + ioff[j0], ib, hipMemcpyHostToDevice, dec->s_up));
-                    FEED_TRY(hipEventRecord(dec->ev_up[c], dec->s_up));
+                    if (ib) PIPE_TRY(hipMemcpyAsync((uint8_t *)dec->d_in.p + ioff[j0], hin + ioff[j0], ib, hipMemcpyHostToDevice, dec->s_up));
+                    PIPE_TRY(hipEventRecord(dec->ev_up[c], dec->s_up));
                     hipStream_t s_k = dec->s_kr[c];
-                    FEED_TRY(hipStreamWaitEvent(s_k, dec->ev_up[c], 0));
+                    PIPE_TRY(hipStreamWaitEvent(s_k, dec->ev_up[c], 0));
                     // (a counter word, a packing cursor and a stream of its own per range: the launches overlap; the range's packed region
                     // starts where its rooms start)
                     strip_lo = (uint32_t)((uint64_t)strip_slices * j0 / m);  // (ranges run side by side: each its own slices)
                     strip_n = (uint32_t)((uint64_t)strip_slices * j1 / m) - strip_lo;
-                    FEED_TRY(launch_runs(j0, j1, dec->d_counter + 8u * c, s_k, ooff[j0], dec->d_counter + 8u * c + 1u));
-                    FEED_TRY(hipEventRecord(dec->ev_k[c], s_k));
+                    PIPE_TRY(launch_runs(j0, j1, dec->d_counter + 8u * c, s_k, ooff[j0], dec->d_counter + 8u * c + 1u));
+                    PIPE_TRY(hipEventRecord(dec->ev_k[c], s_k));
                     if (direct) {
-                        FEED_TRY(hipEventRecord(dec->ev_res[c], s_k));
+                        PIPE_TRY(hipEventRecord(dec->ev_res[c], s_k));
                     } else {
-                    FEED_TRY(hipStreamWaitEvent(dec->s_res, dec->ev_k[c], 0));
+                    PIPE_TRY(hipStreamWaitEvent(dec->s_res, dec->ev_k[c], 0));
                     // the range's results: six short arrays (36 bytes per decoder)
-                    FEED_TRY(hipMemcpyAsync(olen + j0, a.out_len + j0, 8 * (size_t)nn, hipMemcpyDeviceToHost, dec->s_res));
-                    FEED_TRY(hipMemcpyAsync(used + j0, a.in_used + j0, 8 * (size_t)nn, hipMemcpyDeviceToHost, dec->s_res));
-                    FEED_TRY(hipMemcpyAsync(stt + j0, a.status + j0, 4 * (size_t)nn, hipMemcpyDeviceToHost, dec->s_res));
-                    FEED_TRY(hipMemcpyAsync(ad + j0, a.adler + j0, 4 * (size_t)nn, hipMemcpyDeviceToHost, dec->s_res));
-                    FEED_TRY(hipMemcpyAsync(ch + j0, a.chunks + j0, 4 * (size_t)nn, hipMemcpyDeviceToHost, dec->s_res));
-                    FEED_TRY(hipMemcpyAsync(det + 2 * (size_t)j0, a.detail + 2 * (size_t)j0, 8 * (size_t)nn, hipMemcpyDeviceToHost, dec->s_res));
-                    FEED_TRY(hipMemcpyAsync(doff + j0, (const uint64_t *)dec->d_doff.p + j0, 8 * (size_t)nn, hipMemcpyDeviceToHost, dec->s_res));
-                    FEED_TRY(hipEventRecord(dec->ev_res[c], dec->s_res));
+                    PIPE_TRY(hipMemcpyAsync(olen + j0, a.out_len + j0, 8 * (size_t)nn, hipMemcpyDeviceToHost, dec->s_res));
+                    PIPE_TRY(hipMemcpyAsync(used + j0, a.in_used + j0, 8 * (size_t)nn, hipMemcpyDeviceToHost, dec->s_res));
+                    PIPE_TRY(hipMemcpyAsync(stt + j0, a.status + j0, 4 * (size_t)nn, hipMemcpyDeviceToHost, dec->s_res));
+                    PIPE_TRY(hipMemcpyAsync(ad + j0, a.adler + j0, 4 * (size_t)nn, hipMemcpyDeviceToHost, dec->s_res));
+                    PIPE_TRY(hipMemcpyAsync(ch + j0, a.chunks + j0, 4 * (size_t)nn, hipMemcpyDeviceToHost, dec->s_res));
+                    PIPE_TRY(hipMemcpyAsync(det + 2 * (size_t)j0, a.detail + 2 * (size_t)j0, 8 * (size_t)nn, hipMemcpyDeviceToHost, dec->s_res));
+                    PIPE_TRY(hipMemcpyAsync(doff + j0, (const uint64_t *)dec->d_doff.p + j0, 8 * (size_t)nn, hipMemcpyDeviceToHost, dec->s_res));
+                    PIPE_TRY(hipEventRecord(dec->ev_res[c], dec->s_res));
                     }
                 }
                 if (herr == hipSuccess) {
@@ -2253,7 +2196,6 @@ int pzg_decoder_feed(pzg_decoder *dec, const uint32_t *idx, uint32_t m, const ui
                     pcv.notify_all();
                 }
             }
-#undef FEED_TRY
             if (threaded) {
                 drainer.wake();
                 drainer.join();
@@ -2344,11 +2286,7 @@ int pzg_decoder_feed(pzg_decoder *dec, const uint32_t *idx, uint32_t m, const ui
                 if (olen[j]) memcpy(out_base + out_off[j], hout + ooff[j], olen[j] <= ocap[j] ? olen[j] : ocap[j]);
         });
         return PZG_RC_OK;
-    } catch (const std::bad_alloc &) {
-        return PZG_RC_NO_MEMORY;
-    } catch (...) {
-        return PZG_RC_HIP_ERROR;
-    }
+    });
 }
 
 int pzg_decompress(pzg_ctx *ctx, const uint8_t *in, uint64_t in_len, uint8_t *out, uint64_t out_cap,
@@ -2367,7 +2305,7 @@ int pzg_adler32(pzg_ctx *ctx, const uint8_t *buf, uint64_t len, uint32_t init, u
 {
     if (!ctx_live(ctx) || !out || (!buf && len)) return PZG_RC_BAD_ARG;
     if ((flags & PZG_ASYNC) && !(flags & PZG_DEVICE_PTRS)) return PZG_RC_BAD_ARG;
-    try {
+    return guarded(ctx, "pzg_adler32", [&]() -> int {
         Shard &sh = *ctx->shards[0];
         std::lock_guard<std::mutex> g(sh.mu);
         HIP_TRY(ctx, hipSetDevice(sh.device));
@@ -2397,9 +2335,7 @@ int pzg_adler32(pzg_ctx *ctx, const uint8_t *buf, uint64_t len, uint32_t init, u
         HIP_TRY(ctx, hipMemcpyAsync(out, d_res, 4, hipMemcpyDeviceToHost, s));
         HIP_TRY(ctx, hipStreamSynchronize(s));
         return PZG_RC_OK;
-    } catch (...) {
-        return PZG_RC_NO_MEMORY;
-    }
+    });
 }
 
 int pzg_adler32_many(pzg_ctx *ctx, const uint8_t *base, const uint64_t *off, const uint64_t *len, uint32_t *out, uint32_t n,
@@ -2408,16 +2344,18 @@ int pzg_adler32_many(pzg_ctx *ctx, const uint8_t *base, const uint64_t *off, con
     if (!ctx_live(ctx) || !base || !off || !len || !out) return PZG_RC_BAD_ARG;
     if (!(flags & PZG_DEVICE_PTRS) || ctx->shards.size() != 1) return PZG_RC_BAD_ARG;  // device-resident batches only
     if (n == 0) return PZG_RC_OK;
-    Shard &sh = *ctx->shards[0];
-    std::lock_guard<std::mutex> g(sh.mu);
-    HIP_TRY(ctx, hipSetDevice(sh.device));
-    HIP_TRY(ctx, hipEventRecord(sh.ev0, sh.stream));
-    HIP_TRY(ctx, pzg::launch_adler32_many(base, off, len, out, n, sh.num_cus, sh.stream));
-    HIP_TRY(ctx, hipEventRecord(sh.ev1, sh.stream));
-    sh.timed = true;
-    sh.last_was_host = false;
-    if (!(flags & PZG_ASYNC)) HIP_TRY(ctx, hipStreamSynchronize(sh.stream));
-    return PZG_RC_OK;
+    return guarded(ctx, "pzg_adler32_many", [&]() -> int {
+        Shard &sh = *ctx->shards[0];
+        std::lock_guard<std::mutex> g(sh.mu);
+        HIP_TRY(ctx, hipSetDevice(sh.device));
+        HIP_TRY(ctx, hipEventRecord(sh.ev0, sh.stream));
+        HIP_TRY(ctx, pzg::launch_adler32_many(base, off, len, out, n, sh.num_cus, sh.stream));
+        HIP_TRY(ctx, hipEventRecord(sh.ev1, sh.stream));
+        sh.timed = true;
+        sh.last_was_host = false;
+        if (!(flags & PZG_ASYNC)) HIP_TRY(ctx, hipStreamSynchronize(sh.stream));
+        return PZG_RC_OK;
+    });
 }
 
 double pzg_last_kernel_ms(pzg_ctx *ctx)
