@@ -146,7 +146,7 @@ extern "C" {
                               * With pzg_decompress_many_dict a stream with dict_len[i] > 0 decodes with that dictionary as the history
                               * in front of its output, unconditionally -- there is no FDICT bit and no DICTID (zlib's raw
                               * inflateSetDictionary); dict_len[i] = 0: plain raw.  Not combined with PZG_GZIP (PZG_RC_BAD_ARG).
-                              * Raw launches do not use the bundles (PZG_OPT_BUNDLES), and the pzg_decoder_* objects stay zlib-only. */
+                              * Raw launches do not use the bundles (PZG_OPT_BUNDLES).  Resumable raw decoders: pzg_decoder_create_format. */
 #define PZG_CRC32       64u  /* (0.5) only together with PZG_RAW (PZG_RC_BAD_ARG otherwise): adler[i] holds the CRC-32 (RFC 1952 section 8)
                               * of the bytes delivered instead of their Adler-32 -- computed on the device in one more pass over the
                               * output, 0 when out_len[i] > out_cap[i].  Nothing is verified: the caller owns the expected value (a ZIP
@@ -436,7 +436,7 @@ PZG_API int pzg_gzip_layout(pzg_ctx *ctx, const uint8_t *in, uint64_t in_len,
 
 /*
  * decompressIncremental / ZlibDecoder (Zlib.hs:3-8, Monad.hs:163-197; driver Deflate.hs:30-48), batched: a pzg_decoder
- * is n suspended zlib decoders living on the device (a one-device context).  pzg_decoder_feed continues the decoders
+ * is n suspended zlib decoders (gzip or raw ones: pzg_decoder_create_format) living on the device (a one-device context).  pzg_decoder_feed continues the decoders
  * idx[0..m) (idx = NULL: all n, m ignored) -- one launch, one wavefront per decoder -- as far as their input and
  * output room go.  For decoder k = idx[j]:
  *   in_base + in_off[j] .. + in_len[j]   the bytes the last call did not consume (from its in_used on) followed by
@@ -462,6 +462,35 @@ PZG_API int pzg_gzip_layout(pzg_ctx *ctx, const uint8_t *in, uint64_t in_len,
  */
 typedef struct pzg_decoder pzg_decoder;
 PZG_API int  pzg_decoder_create(pzg_ctx *ctx, uint32_t n, pzg_decoder **out);  /* takes a reference on ctx */
+/* (0.5) pzg_decoder_create for another container.  format: 0 (zlib, the same as pzg_decoder_create), PZG_GZIP or PZG_RAW; anything else
+ * (PZG_GZIP | PZG_RAW too) is PZG_RC_BAD_ARG.  All n decoders of the object share the format, pzg_decoder_reset keeps it, and
+ * pzg_decoder_feed is what it is for zlib decoders: its suspension protocol, its chunks[] rule (the publication rule does not depend on
+ * the wrapper), its pipelined path for large feeds.
+ * THE RULE that decides every corner: however the input is cut into feeds and the rooms are sized, the concatenation of the delivered
+ * bytes, the terminal state and its detail, the last adler[j] and the sum of the in_used[j] of all calls are what pzg_decompress_many
+ * gives with the same flag over the whole input as one stream with enough capacity.  (For a decoder that ends with an error met
+ * inside the blocks in_used is unspecified, as it is for a failed stream of that call -- the batch kernels have read ahead of the
+ * token that fails -- and never more than what the call was given.)  A terminal error is reported once the batch path would have met it, never earlier because a piece ended.
+ * PZG_RAW: no header, no trailer.  The first block header is at bit 0 of the first byte fed; the state is PZG_OK when the final block
+ *   ends, and in_used counts up to and including the byte that holds its last bit -- what follows is left alone.  adler[j] is the
+ *   running Adler-32 of everything delivered so far, reported and never checked.  PZG_E_HDR_*, PZG_E_CHECKSUM and PZG_E_DICT cannot
+ *   occur; with final_in set, input that ends before the final block does is PZG_E_TRUNCATED; detail[1] of PZG_E_HUFF_BUILD counts
+ *   bits from the first bit ever fed.
+ * PZG_GZIP: a series of RFC 1952 members, as the batch gzip path reads them.
+ *   A member header is read as a whole: if the input ends inside it and final_in is not set, the decoder suspends at the header's
+ *   first byte (PZG_DEC_NEED_INPUT, in_used stops in front of the header; the next call reads it again from its start -- so a
+ *   header, FEXTRA, FNAME and FCOMMENT included, must fit one feed); with final_in a short header is PZG_E_TRUNCATED.  Header errors
+ *   are PZG_E_GZIP_HEADER with the batch path's detail words.
+ *   The 8-byte trailer is read as a whole, under the same rule.  There the member's ISIZE is checked (PZG_E_GZIP_ISIZE) and its
+ *   CRC-32 is folded into the CRC-32 the whole output must have.  Behind a trailer: fewer than 2 bytes left and no final_in --
+ *   PZG_DEC_NEED_INPUT (a decoder may then still hold the trailer unread); 1f 8b -- the next member follows; anything else, or the
+ *   end of the input with final_in -- PZG_OK, the trailing bytes stay unconsumed.
+ *   adler[j] is the running CRC-32 of everything delivered so far, carried across the calls: a pass behind the decode kernel, on the
+ *   same stream and in front of every download, takes the CRC-32 of each fed decoder's delivery of this call and appends it.  When
+ *   a decoder has ended with PZG_OK or PZG_E_GZIP_ISIZE the pass holds the running value against the expected one; a mismatch makes
+ *   the state PZG_E_CHECKSUM with detail = {expected, ours} -- the CRC-32 is looked at first, as zlib does -- now and for every
+ *   later call on that decoder. */
+PZG_API int  pzg_decoder_create_format(pzg_ctx *ctx, uint32_t n, uint32_t format, pzg_decoder **out);
 PZG_API void pzg_decoder_destroy(pzg_decoder *dec);  /* legal before or after pzg_shutdown(ctx); NULL is ignored */
 PZG_API int  pzg_decoder_reset(pzg_decoder *dec, const uint32_t *idx, uint32_t m);  /* those decoders start a new stream */
 /* (0.5) What the last LARGE pzg_decoder_feed call of `dec` (512 decoders or 64 MiB of rooms and more: the pipelined path) spent where, in

@@ -22,3 +22,4 @@ from .zlib import (  # noqa: F401
 )
 from .indexed import Index, adler32_combine, crc32_combine  # noqa: F401
 from .gzfile import MemberIndex, decompress_gzip_file  # noqa: F401
+from .incremental import FORMATS, DecoderPool, decompress_incremental, decompressIncremental  # noqa: F401

@@ -52,7 +52,7 @@ DEFAULT_RING_BITS = 11
 # every symbol include/pzg.h declares
 SYMBOLS = [
     "pzg_init", "pzg_init_mask", "pzg_init_devices", "pzg_host_alloc", "pzg_host_free", "pzg_device_count", "pzg_adler32_many", "pzg_decompress_many_dict", "pzg_decompress_many_sharded",
-    "pzg_decoder_create", "pzg_decoder_destroy", "pzg_decoder_reset", "pzg_decoder_feed", "pzg_decoder_last_feed_ms", "pzg_shutdown", "pzg_set_stream", "pzg_reset_stream", "pzg_set_option", "pzg_sync", "pzg_decompress_many", "pzg_decompress",
+    "pzg_decoder_create", "pzg_decoder_create_format", "pzg_decoder_destroy", "pzg_decoder_reset", "pzg_decoder_feed", "pzg_decoder_last_feed_ms", "pzg_shutdown", "pzg_set_stream", "pzg_reset_stream", "pzg_set_option", "pzg_sync", "pzg_decompress_many", "pzg_decompress",
     "pzg_adler32", "pzg_error_message", "pzg_last_kernel_ms", "pzg_strerror", "pzg_last_error", "pzg_version",
     "pzg_index_build", "pzg_decompress_many_segments", "pzg_index_scan", "pzg_gzip_find_members", "pzg_gzip_layout",
 ]
@@ -133,6 +133,9 @@ def lib():
     L.pzg_decompress_many_sharded.restype = C.c_int
     L.pzg_decoder_create.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]
     L.pzg_decoder_create.restype = C.c_int
+    if hasattr(L, "pzg_decoder_create_format"):  # (PZG_LIB may name an older build, as above: bench comparisons against a parent commit)
+        L.pzg_decoder_create_format.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
+        L.pzg_decoder_create_format.restype = C.c_int
     L.pzg_decoder_destroy.argtypes = [C.c_void_p]
     L.pzg_decoder_destroy.restype = None
     L.pzg_decoder_reset.argtypes = [C.c_void_p, u32p, C.c_uint32]

@@ -31,7 +31,7 @@ READ_CHUNK = 32768  # L.readFile hands out defaultChunkSize pieces (SURVEY.md 8a
 
 
 def incremental_throughput(ctx, streams: List[bytes], plain: List[bytes], n_decoders: int = 4096, piece: int = 32768,
-                           room: int = 192 * 1024, passes: int = 5) -> Dict[str, object]:
+                           room: int = 192 * 1024, passes: int = 5, format: int = 0) -> Dict[str, object]:
     """Throughput of the incremental path (Benchmark.hs:53-70 benches `decompressIncremental` per fixture; this is its
     batched form): n_decoders resumable decoders, decoder k on streams[k % len(streams)], every one fed `piece` input
     bytes per pzg_decoder_feed call -- one launch per call, host buffers both ways.  Only the feed calls are timed (the
@@ -43,7 +43,11 @@ def incremental_throughput(ctx, streams: List[bytes], plain: List[bytes], n_deco
     from . import _ffi
     L = _ffi.lib()
     h = C.c_void_p()
-    _ffi.check(L.pzg_decoder_create(ctx.handle, n_decoders, C.byref(h)), ctx.handle)
+    # format: 0 -- zlib streams (pzg_decoder_create); _ffi.GZIP / _ffi.RAW -- the streams are gzip members / raw (pzg_decoder_create_format)
+    if format == 0:
+        _ffi.check(L.pzg_decoder_create(ctx.handle, n_decoders, C.byref(h)), ctx.handle)
+    else:
+        _ffi.check(L.pzg_decoder_create_format(ctx.handle, n_decoders, format, C.byref(h)), ctx.handle)
     P = len(streams)
 
     def one_pass():

@@ -294,6 +294,10 @@ struct ResumeState {
     uint32_t dist_sub_used;  // second-level entries of the distance code (strip_span() asks: ADVICE r5)
     uint64_t in_total;     // input bytes consumed by the earlier calls (positions in error details count from the stream start)
     uint32_t QT[64];
+    // gzip decoders only (zero otherwise)
+    uint32_t crc;          // running CRC-32 of everything delivered so far (kept by resume_crc_kernel, never by the decoder)
+    uint32_t gz_expect;    // the CRC-32 the output so far must have according to the member trailers read (crc32_append)
+    uint64_t gz_mstart;    // the output position where the current member began
 };
 
 // A suspended decoder's slot in HBM: ResumeState | the wave's LDS image | (small rings) its 32 KiB history.
@@ -491,15 +495,16 @@ struct BitReader {
 
 // ---- decoder state (all wave-uniform) -----------------------------------------------------------
 // GZIP: the streams are RFC 1952 members (an extension; its own kernel instances, so the zlib ones carry none of it)
-// RES: the resumable instance (decompressIncremental): suspends when the input or the output room runs out
+// RES: the resumable instance (decompressIncremental): suspends when the input or the output room runs out; with GZIP or RAW the
+// resumable gzip / raw decoders (pzg_decoder_create_format), which differ from it in the header and trailer phases of resume_decode() only
 // RAW: the streams are bare RFC 1951 (an extension: what a ZIP member holds): no header, no trailer, nothing checked; its own kernel
 // instances again (pzg_inflate_kernel.h inflate_raw_kernel)
 // SEG: a raw decoder for the pieces of ONE indexed stream (an extension; pzg_kernels_b.hip inflate_seg_kernel): it starts at a bit
 // inside its first byte, may stop at the end of a block that is not the final one, and can record access points as it goes
 template <int RING_BITS, bool GZIP = false, bool RES = false, bool RAW = false, bool SEG = false>
 struct Decoder {
-    static_assert(!RAW || (!GZIP && !RES), "a raw stream has no container and no resumable instance");
-    static_assert(!SEG || RAW, "segments are pieces of a raw stream");
+    static_assert(!RAW || !GZIP, "a raw stream has no container");
+    static_assert(!SEG || (RAW && !RES), "segments are pieces of a raw stream, decoded in one go");
     static constexpr uint32_t RING = 1u << RING_BITS;
     static constexpr uint32_t RMASK = RING - 1u;
     static constexpr uint32_t FLUSH_AT = RING - 1024u;
@@ -560,6 +565,7 @@ struct Decoder {
     uint32_t phase, bfinal_cur, stored_left, deferred, ow, chunks;
     uint64_t susp_pos;          // stream bit position (relative to this call's input) at which the next call resumes
     uint64_t in_total_bits;     // 8 * the input bytes consumed by earlier calls
+    uint64_t gz_mstart;         // gzip: the output position where the current member began
     uint32_t qn;                // tokens waiting in QT (lanes 0..qn-1, never more than QCAP), see queue_append()
     LaneVec<uint32_t> QT;
     // SEG only (set by the caller before run(); bit offsets count from bit 0 of the input's first byte)
@@ -4571,9 +4577,16 @@ struct Decoder {
         for (;;) {
             pin_uniform();
             if (phase == PH_HEADER) {
-                const int st = zlib_header();
-                if (truncated_suspends(st)) return suspend_input(0);
-                if (st) return st;
+                if constexpr (GZIP) {  // a member header, read as a whole: running out of input inside it suspends at its first byte
+                    const uint64_t hpos = stream_bit_pos();
+                    const int st = gzip_header();
+                    if (truncated_suspends(st)) return suspend_input(hpos);
+                    if (st) return st;
+                } else if constexpr (!RAW) {  // (raw: the first block header is at bit 0 of the first byte fed)
+                    const int st = zlib_header();
+                    if (truncated_suspends(st)) return suspend_input(0);
+                    if (st) return st;
+                }
                 phase = PH_BLOCK;
             } else if (phase == PH_BLOCK) {
                 const uint64_t blk_pos = stream_bit_pos();
@@ -4640,6 +4653,35 @@ struct Decoder {
                 if (st) return st;
                 move_window_check();  // Deflate.hs:47
                 phase = bfinal_cur ? PH_TRAILER : PH_BLOCK;
+            } else if (RAW && phase == PH_TRAILER) {  // a raw stream ends with its final block: what follows is left alone
+                phase = PH_DONE;
+                return ST_OK;
+            } else if (GZIP && phase == PH_TRAILER) {
+                // gzip_members(), one turn of its loop: CRC-32 and ISIZE as a whole (8 bytes from the next byte boundary), then the
+                // two bytes that say whether a further member follows.  Nothing is consumed until all of it can be decided.
+                const uint64_t tpos = stream_bit_pos();
+                const int64_t have = br.avail() - (int64_t)((8u - (br.rp & 7u)) & 7u);
+                if (have < 64) {
+                    if (!res_final) return suspend_input(tpos);
+                    br.align_to_byte();
+                    return fail(ST_TRUNCATED, 0, 0);
+                }
+                if (have < 80 && !res_final) return suspend_input(tpos);  // (whether a member follows is not known yet)
+                br.align_to_byte();
+                const uint32_t crc = br.peek32();
+                br.drop(32);
+                const uint32_t isize = br.peek32();
+                br.drop(32);
+                const uint64_t mlen = op - gz_mstart;
+                gz_expect = crc32_append(gz_expect, crc, mlen);
+                // (reported unless the CRC-32 is wrong as well: resume_crc_kernel looks at that first, as zlib does)
+                if (isize != (uint32_t)mlen) return fail(ST_GZIP_ISIZE, isize, (uint32_t)mlen);
+                gz_mstart = op;
+                if (br.avail() < 16 || (br.peek32() & 0xffffu) != 0x8b1fu) {  // no further member follows
+                    phase = PH_DONE;
+                    return ST_OK;
+                }
+                phase = PH_HEADER;
             } else if (phase == PH_TRAILER) {
                 const uint64_t tpos = stream_bit_pos();
                 // (asked for before zlib_trailer() flushes: a flush to an odd position must be the last one)
@@ -4723,7 +4765,8 @@ struct Decoder {
         dict = nullptr;
         dict_len = 0;
         hist_extra = 0;
-        gz_expect = 0;
+        gz_expect = GZIP ? rs->gz_expect : 0u;
+        gz_mstart = GZIP ? rs->gz_mstart : 0u;
         pend_m0 = pend_m1 = 0;
         pend_pos = 0;
         in_byte0 = 0;
@@ -4790,7 +4833,8 @@ struct Decoder {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no fetch into this wave's LDS may outlive the call
 #endif
         wave_sync();
-        uint64_t used = susp_pos >> 3;
+        // (gzip, raw: a decoder that has ended is done with the byte that holds the last bit it read, as the batch kernels are)
+        uint64_t used = ((GZIP || RAW) && phase == PH_DONE ? susp_pos + 7u : susp_pos) >> 3;
         if (used > in_len) used = in_len;
         {   // save
             lds_image_copy<true>(lds_image, op);
@@ -4820,13 +4864,17 @@ struct Decoder {
                 rs->detail0 = detail0;
                 rs->detail1 = detail1;
                 rs->in_total += used;
+                if constexpr (GZIP) {
+                    rs->gz_expect = gz_expect;
+                    rs->gz_mstart = gz_mstart;
+                }
             }
         }
         res->status = st == ST_NEED_INPUT || st == ST_OUT_FULL ? st : status;
         res->detail0 = detail0;
         res->detail1 = detail1;
         res->adler = (adler_b << 16) | adler_a;
-        res->gz_crc = 0;
+        res->gz_crc = GZIP ? gz_expect : 0u;
         res->out_len = flushed - flushed0;  // bytes delivered by THIS call
         res->in_used = used;
         *chunks_out = chunks;

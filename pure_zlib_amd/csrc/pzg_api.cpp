@@ -1720,6 +1720,7 @@ struct pzg_decoder {
     pzg_ctx *ctx = nullptr;  // holds one reference (ctx_unref in pzg_decoder_destroy): never dangles
     int device = 0;
     uint32_t n = 0;
+    uint32_t format = 0;  // 0 (zlib), PZG_GZIP or PZG_RAW: what all n decoders decode (pzg_decoder_create_format)
     size_t stride = 0;
     uint8_t *d_state = nullptr;  // n x stride: ResumeState + LDS image per decoder
     uint32_t *d_counter = nullptr;
@@ -1771,10 +1772,14 @@ int pzg_decoder_last_feed_ms(pzg_decoder *dec, double out[5])
     });
 }
 
-int pzg_decoder_create(pzg_ctx *ctx, uint32_t n, pzg_decoder **out)
+int pzg_decoder_create(pzg_ctx *ctx, uint32_t n, pzg_decoder **out) { return pzg_decoder_create_format(ctx, n, 0u, out); }
+
+int pzg_decoder_create_format(pzg_ctx *ctx, uint32_t n, uint32_t format, pzg_decoder **out)
 {
     if (out) *out = nullptr;
     if (!ctx_live(ctx) || !out || n == 0 || ctx->shards.size() != 1) return PZG_RC_BAD_ARG;
+    static_assert(pzg::RESUME_FORMAT_GZIP == PZG_GZIP && pzg::RESUME_FORMAT_RAW == PZG_RAW, "the launcher's formats are the header's flags");
+    if (format != pzg::RESUME_FORMAT_ZLIB && format != PZG_GZIP && format != PZG_RAW) return PZG_RC_BAD_ARG;
     pzg_decoder *d = nullptr;
     const int rc = guarded(ctx, "pzg_decoder_create", [&]() -> int {
         Shard &sh = *ctx->shards[0];
@@ -1784,6 +1789,7 @@ int pzg_decoder_create(pzg_ctx *ctx, uint32_t n, pzg_decoder **out)
         d->ctx = ctx;
         d->device = sh.device;
         d->n = n;
+        d->format = format;
         d->stride = pzg::resume_state_bytes();
         hipError_t e;
         if (hipMalloc((void **)&d->d_state, d->stride * (size_t)n) != hipSuccess || hipMalloc((void **)&d->d_counter, 256) != hipSuccess)
@@ -1984,7 +1990,7 @@ int pzg_decoder_feed(pzg_decoder *dec, const uint32_t *idx, uint32_t m, const ui
                     r.dense_cursor = dense_cursor;
                     r.dense_off = (dense_host ? dense_host : (uint64_t *)dec->d_doff.p) + j0;
                 }
-                const hipError_t e = pzg::launch_resume(r, num_cus, st);
+                const hipError_t e = pzg::launch_resume(r, dec->format, num_cus, st);
                 if (e != hipSuccess) return e;
                 j0 = j1;
             }

@@ -83,25 +83,27 @@ __device__ __forceinline__ uint32_t crc_zero_bytes_factor(uint64_t n, uint32_t s
 // stream's status.  Without it (PZG_RAW | PZG_CRC32): report only -- adler[i] gets the CRC-32 of the bytes delivered, 0 for a stream
 // that outgrew its capacity; nothing is compared, nothing else is written and no gz_expect arena exists.
 constexpr uint32_t CRC_BLOCK = 1024u, CRC_WAVES = 4u;
-template <bool VERIFY>
-__device__ __forceinline__ void crc32_pass(const InflateArgs &a)
+struct CrcLds {
+    uint32_t T[4][256], ADV[4][256];
+};
+// the tables, built by the whole workgroup (64 * CRC_WAVES threads); returns this lane's x^(8 * 16 * (63 - lane))
+__device__ __forceinline__ uint32_t crc32_tables(CrcLds &L)
 {
-    __shared__ uint32_t T[4][256], ADV[4][256];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
     for (uint32_t v = tid; v < 256u; v += 64u * CRC_WAVES) {
         uint32_t r = v;
         for (int k = 0; k < 8; ++k) r = (r >> 1) ^ (0xedb88320u & (0u - (r & 1u)));
-        T[0][v] = r;
+        L.T[0][v] = r;
     }
     __syncthreads();
     const uint32_t f_adv = crc_zero_bytes_factor(CRC_BLOCK - 16u, 0u);
     for (uint32_t v = tid; v < 256u; v += 64u * CRC_WAVES) {
-        uint32_t r = T[0][v];
+        uint32_t r = L.T[0][v];
         for (int k = 1; k < 4; ++k) {
-            r = (r >> 8) ^ T[0][r & 0xffu];
-            T[k][v] = r;
+            r = (r >> 8) ^ L.T[0][r & 0xffu];
+            L.T[k][v] = r;
         }
-        for (int k = 0; k < 4; ++k) ADV[k][v] = gf2_mulmod(v << (8 * k), f_adv);
+        for (int k = 0; k < 4; ++k) L.ADV[k][v] = gf2_mulmod(v << (8 * k), f_adv);
     }
     // x^(8 * 16 * (63 - lane)): what moves this lane's accumulator to the end of the stream
     uint32_t f_lane = 0x80000000u;
@@ -114,6 +116,47 @@ __device__ __forceinline__ void crc32_pass(const InflateArgs &a)
         }
     }
     __syncthreads();
+    return f_lane;
+}
+// One wave, one stream: the CRC-32 of p[0 .. len) (0 for none), valid in lane 0.  The one copy of the block scheme: the batch
+// passes below and the resumable decoders' pass (resume_crc_kernel) both run it.
+__device__ __forceinline__ uint32_t crc32_stream(const CrcLds &L, uint32_t f_lane, uint32_t lane, const uint8_t *p, uint64_t len)
+{
+    const uint64_t pad = (CRC_BLOCK - (len & (CRC_BLOCK - 1u))) & (CRC_BLOCK - 1u);  // zero bytes in front
+    const uint64_t nblk = (len + pad) / CRC_BLOCK;
+    uint32_t acc = 0;
+    for (uint64_t blk = 0; blk < nblk; ++blk) {
+        const uint64_t pp = blk * CRC_BLOCK + 16u * lane;  // this lane's chunk in the padded stream
+        uint32_t w[4] = {0u, 0u, 0u, 0u};
+        if (blk != 0u || pad == 0u) {  // (wave-uniform) the whole block is stream
+            __builtin_memcpy(w, p + (pp - pad), 16);
+        } else {  // the first block of a stream whose length is no multiple of 1 KiB: bytes in front of the stream are zero
+            for (uint32_t t = 0; t < 16u; ++t) {
+                const uint64_t q = pp + t;
+                const uint32_t byte = q >= pad ? (uint32_t)p[q - pad] : 0u;
+                w[t >> 2] |= byte << (8u * (t & 3u));
+            }
+        }
+        uint32_t reg = L.ADV[3][acc >> 24] ^ L.ADV[2][(acc >> 16) & 0xffu] ^ L.ADV[1][(acc >> 8) & 0xffu] ^ L.ADV[0][acc & 0xffu];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            reg ^= w[k];
+            reg = L.T[3][reg & 0xffu] ^ L.T[2][(reg >> 8) & 0xffu] ^ L.T[1][(reg >> 16) & 0xffu] ^ L.T[0][reg >> 24];
+        }
+        acc = reg;
+    }
+    uint32_t reg = gf2_mulmod(acc, f_lane);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) reg ^= (uint32_t)__shfl_xor((int)reg, o, 64);
+    reg ^= gf2_mulmod(0xffffffffu, crc_zero_bytes_factor(len, 0u));  // the initial register, advanced over the stream
+    return len ? ~reg : 0u;
+}
+template <bool VERIFY>
+__device__ __forceinline__ void crc32_pass(const InflateArgs &a)
+{
+    __shared__ CrcLds L;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t f_lane = crc32_tables(L);
     for (uint32_t i = blockIdx.x * CRC_WAVES + wave; i < a.n; i += gridDim.x * CRC_WAVES) {
         // every member's ISIZE was checked as it was decoded; a mismatch is reported unless the CRC-32 is wrong as well
         // (zlib's order).  A stream that failed otherwise gets the CRC-32 of the bytes it delivered, nothing is checked.
@@ -125,36 +168,8 @@ __device__ __forceinline__ void crc32_pass(const InflateArgs &a)
             if (!VERIFY && lane == 0u && a.adler) a.adler[i] = 0u;  // (the raw kernels left the Adler-32 there)
             continue;
         }
-        const uint8_t *p = a.out_base + a.out_off[i];
-        const uint64_t pad = (CRC_BLOCK - (len & (CRC_BLOCK - 1u))) & (CRC_BLOCK - 1u);  // zero bytes in front
-        const uint64_t nblk = (len + pad) / CRC_BLOCK;
-        uint32_t acc = 0;
-        for (uint64_t blk = 0; blk < nblk; ++blk) {
-            const uint64_t pp = blk * CRC_BLOCK + 16u * lane;  // this lane's chunk in the padded stream
-            uint32_t w[4] = {0u, 0u, 0u, 0u};
-            if (blk != 0u || pad == 0u) {  // (wave-uniform) the whole block is stream
-                __builtin_memcpy(w, p + (pp - pad), 16);
-            } else {  // the first block of a stream whose length is no multiple of 1 KiB: bytes in front of the stream are zero
-                for (uint32_t t = 0; t < 16u; ++t) {
-                    const uint64_t q = pp + t;
-                    const uint32_t byte = q >= pad ? (uint32_t)p[q - pad] : 0u;
-                    w[t >> 2] |= byte << (8u * (t & 3u));
-                }
-            }
-            uint32_t reg = ADV[3][acc >> 24] ^ ADV[2][(acc >> 16) & 0xffu] ^ ADV[1][(acc >> 8) & 0xffu] ^ ADV[0][acc & 0xffu];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                reg ^= w[k];
-                reg = T[3][reg & 0xffu] ^ T[2][(reg >> 8) & 0xffu] ^ T[1][(reg >> 16) & 0xffu] ^ T[0][reg >> 24];
-            }
-            acc = reg;
-        }
-        uint32_t reg = gf2_mulmod(acc, f_lane);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) reg ^= (uint32_t)__shfl_xor((int)reg, o, 64);
+        const uint32_t ours = crc32_stream(L, f_lane, lane, a.out_base + a.out_off[i], len);
         if (lane == 0u) {
-            reg ^= gf2_mulmod(0xffffffffu, crc_zero_bytes_factor(len, 0u));  // the initial register, advanced over the stream
-            const uint32_t ours = len ? ~reg : 0u;
             if (a.adler) a.adler[i] = ours;
             if (VERIFY) {
                 const uint32_t theirs = a.gz_expect[2 * (size_t)i];
@@ -171,6 +186,49 @@ __device__ __forceinline__ void crc32_pass(const InflateArgs &a)
 }
 __global__ __launch_bounds__(64 * CRC_WAVES) void crc32_verify_kernel(InflateArgs a) { crc32_pass<true>(a); }
 __global__ __launch_bounds__(64 * CRC_WAVES) void crc32_report_kernel(InflateArgs a) { crc32_pass<false>(a); }
+
+// The resumable gzip decoders' pass (pzg_decoder_create_format with PZG_GZIP), behind resume_gzip_kernel on the same stream and in
+// front of every download: one wave per fed decoder takes the CRC-32 of what the decoder delivered in THIS call, appends it to the
+// running value in the decoder's state (shift by the delivery's length, add) and reports the running value in adler[].  A decoder
+// that has ended with PZG_OK or PZG_E_GZIP_ISIZE is held against what its members' trailers ask for (ResumeState::gz_expect): a
+// mismatch rewrites the state to PZG_E_CHECKSUM, in the call's results and in the decoder's slot -- the batch path's rule, the
+// CRC-32 is looked at first.  (A decoder fed again after it has ended delivers nothing: the same comparison, the same answer.)
+__global__ __launch_bounds__(64 * CRC_WAVES) void resume_crc_kernel(ResumeArgs a)
+{
+    __shared__ CrcLds L;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t f_lane = crc32_tables(L);
+    for (uint32_t i = blockIdx.x * CRC_WAVES + wave; i < a.n; i += gridDim.x * CRC_WAVES) {
+        const uint64_t len = a.out_len[i];
+        if (len > a.out_cap[i]) continue;  // (never: a resumable decoder produces nothing past its room)
+        const uint32_t part = crc32_stream(L, f_lane, lane, a.out_base + a.out_off[i], len);
+        if (lane == 0u) {
+            ResumeState *rs = (ResumeState *)(void *)(a.state_base + (size_t)i * a.state_stride);
+            const uint32_t run = len ? gf2_mulmod(rs->crc, crc_zero_bytes_factor(len, 0u)) ^ part : rs->crc;
+            rs->crc = run;
+            if (a.adler) a.adler[i] = run;
+            const int32_t st = a.status[i];
+            const uint32_t theirs = rs->gz_expect;
+            if ((st == ST_OK || st == ST_GZIP_ISIZE) && theirs != run) {
+                a.status[i] = ST_CHECKSUM;
+                rs->status = ST_CHECKSUM;
+                rs->detail0 = theirs;
+                rs->detail1 = run;
+                if (a.detail) {
+                    a.detail[2 * (size_t)i] = theirs;
+                    a.detail[2 * (size_t)i + 1] = run;
+                }
+            }
+        }
+    }
+}
+hipError_t launch_resume_crc(const ResumeArgs &a, int num_cus, hipStream_t stream)
+{
+    if (a.n == 0) return hipSuccess;
+    const uint32_t cwg = (a.n + CRC_WAVES - 1u) / CRC_WAVES;
+    hipLaunchKernelGGL(resume_crc_kernel, dim3(cwg < (uint32_t)num_cus * 8u ? cwg : (uint32_t)num_cus * 8u), dim3(64 * CRC_WAVES), 0, stream, a);
+    return hipGetLastError();
+}
 
 // stream-waves of a launch: the residency of the chip, or one per stream if there are fewer
 static uint32_t launch_waves(int ring_bits, int num_cus, uint32_t n, uint32_t gzip)

@@ -1,6 +1,6 @@
 // pzg_kernels_b.hip -- the kernels that are compiled WITHOUT the compiler's SDWA peephole (Makefile: KERNELFLAGS_B):
 //
-//   inflate_resume_kernel           the resumable decoder (decompressIncremental)
+//   inflate_resume_kernel           the resumable decoder (decompressIncremental); resume_gzip_kernel, resume_raw_kernel: its gzip and raw forms
 //   inflate_kernel<RB, *, true>     the gzip instances
 //   inflate_raw_kernel<RB, *>       the raw instances
 //   inflate_seg_kernel              the segment instance (indexed streams), and index_windows_kernel beside it
@@ -330,85 +330,125 @@ const uint64_t *members_layout_total(uint64_t m, const uint8_t *scratch) { retur
 #define PZG_RES_WAVES_PER_SIMD 4
 #endif
 constexpr int RES_RING = PZG_RES_RING;
+// What a stream-wave of the three resume kernels does; DEC is the zlib, the gzip or the raw instance of the resumable decoder.  One
+// copy of the text, expanded in each kernel and not a __device__ function template that the three call: as a function -- the
+// argument block handed over by reference, by value or as a pointer into the kernel-argument segment, all three were built -- the
+// zlib kernel spilled a vector register (8 bytes of scratch per lane), which it does not when the body stands in the kernel itself
+// and reads the kernel's own parameter.
+#define PZG_RESUME_WAVE(DEC)  \
+    __shared__ WaveLds<RES_RING> lds;                                                                                                    \
+    for (;;) {                                                                                                                             \
+        uint32_t i = 0;                                                                                                                    \
+        if (threadIdx.x == 0) i = atomicAdd(a.counter, 1u);                                                                                \
+        i = uni(i);                                                                                                                        \
+        if (i >= a.n) break;                                                                                                               \
+        uint8_t *slot = a.state_base + (size_t)i * a.state_stride;                                                                         \
+        ResumeState *rs = (ResumeState *)slot;                                                                                             \
+        uint32_t *image = (uint32_t *)(slot + ResumeSlot<RES_RING>::IMAGE_OFF);                                                            \
+        DEC dec(lds);                                                                                                                      \
+        if (a.strip && blockIdx.x < a.strip_waves) dec.strip = a.strip + (size_t)blockIdx.x * DEC::STRIP_WORDS;                            \
+        StreamResult r;                                                                                                                    \
+        uint32_t chunks = 0;                                                                                                               \
+        dec.run_resume(rs, image, slot + ResumeSlot<RES_RING>::HIST_OFF, a.in_base + a.in_off[i], a.in_len[i], a.out_base + a.out_off[i],  \
+                       a.out_cap[i], a.final_in ? (uint32_t)a.final_in[i] : 0u, &r, &chunks);                                              \
+        if (threadIdx.x == 0) {                                                                                                            \
+            a.status[i] = r.status;                                                                                                        \
+            a.out_len[i] = r.out_len;                                                                                                      \
+            a.in_used[i] = r.in_used;                                                                                                      \
+            a.chunks[i] = chunks;                                                                                                          \
+            if (a.adler) a.adler[i] = r.adler;                                                                                             \
+            if (a.detail) {                                                                                                                \
+                a.detail[2 * (size_t)i] = r.detail0;                                                                                       \
+                a.detail[2 * (size_t)i + 1] = r.detail1;                                                                                   \
+            }                                                                                                                              \
+        }                                                                                                                                  \
+        if (a.dense) {                                                                                                                     \
+            /* what this decoder delivered, once more, behind what the others of its range delivered: the host then fetches ONE */         \
+            /* linear span per range instead of rooms that are mostly empty (the bytes are this wave's own stores of a moment */           \
+            /* ago: L2 hits; 64 lanes x 16 bytes per step, four steps in flight) */                                                        \
+            typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));                                                                    \
+            const uint32_t nv = (uint32_t)((r.out_len + 15u) >> 4);                                                                        \
+            uint32_t at = 0;                                                                                                               \
+            if (threadIdx.x == 0) at = atomicAdd(a.dense_cursor, nv);                                                                      \
+            at = uni(at);                                                                                                                  \
+            const uint64_t off = a.dense_region + 16ull * at;                                                                              \
+            if (threadIdx.x == 0) a.dense_off[i] = off;                                                                                    \
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  /* the flushes' stores have landed */                                        \
+            const u32x4 *src = (const u32x4 *)(const void *)(a.out_base + a.out_off[i]);                                                   \
+            u32x4 *dst = (u32x4 *)(void *)(a.dense + off);                                                                                 \
+            for (uint32_t v0 = 0; v0 < nv; v0 += 256u) {                                                                                   \
+                u32x4 t[4];                                                                                                                \
+_Pragma("unroll")                                                                                                                          \
+                for (uint32_t q = 0; q < 4u; ++q) {                                                                                        \
+                    const uint32_t v = v0 + 64u * q + threadIdx.x;                                                                         \
+                    t[q] = __builtin_nontemporal_load(src + (v < nv ? v : nv - 1u));                                                       \
+                }                                                                                                                          \
+_Pragma("unroll")                                                                                                                          \
+                for (uint32_t q = 0; q < 4u; ++q) {                                                                                        \
+                    const uint32_t v = v0 + 64u * q + threadIdx.x;                                                                         \
+                    if (v < nv) dst[v] = t[q];                                                                                             \
+                }                                                                                                                          \
+            }                                                                                                                              \
+        }                                                                                                                                  \
+        __syncthreads();                                                                                                                   \
+    }                                                                                                                                      \
+    do {} while (0)
 __global__ __launch_bounds__(64, RES_RING == 15 ? 1 : PZG_RES_WAVES_PER_SIMD) void inflate_resume_kernel(ResumeArgs a)
 {
-    __shared__ WaveLds<RES_RING> lds;
-    for (;;) {
-        uint32_t i = 0;
-        if (threadIdx.x == 0) i = atomicAdd(a.counter, 1u);
-        i = uni(i);
-        if (i >= a.n) break;
-        uint8_t *slot = a.state_base + (size_t)i * a.state_stride;
-        ResumeState *rs = (ResumeState *)slot;
-        uint32_t *image = (uint32_t *)(slot + ResumeSlot<RES_RING>::IMAGE_OFF);
-        Decoder<RES_RING, false, true> dec(lds);
-        if (a.strip && blockIdx.x < a.strip_waves) dec.strip = a.strip + (size_t)blockIdx.x * Decoder<RES_RING, false, true>::STRIP_WORDS;
-        StreamResult r;
-        uint32_t chunks = 0;
-        dec.run_resume(rs, image, slot + ResumeSlot<RES_RING>::HIST_OFF, a.in_base + a.in_off[i], a.in_len[i], a.out_base + a.out_off[i],
-                       a.out_cap[i], a.final_in ? (uint32_t)a.final_in[i] : 0u, &r, &chunks);
-        if (threadIdx.x == 0) {
-            a.status[i] = r.status;
-            a.out_len[i] = r.out_len;
-            a.in_used[i] = r.in_used;
-            a.chunks[i] = chunks;
-            if (a.adler) a.adler[i] = r.adler;
-            if (a.detail) {
-                a.detail[2 * (size_t)i] = r.detail0;
-                a.detail[2 * (size_t)i + 1] = r.detail1;
-            }
-        }
-        if (a.dense) {
-            // what this decoder delivered, once more, behind what the others of its range delivered: the host then fetches ONE
-            // linear span per range instead of rooms that are mostly empty (the bytes are this wave's own stores of a moment
-            // ago: L2 hits; 64 lanes x 16 bytes per step, four steps in flight)
-            typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-            const uint32_t nv = (uint32_t)((r.out_len + 15u) >> 4);
-            uint32_t at = 0;
-            if (threadIdx.x == 0) at = atomicAdd(a.dense_cursor, nv);
-            at = uni(at);
-            const uint64_t off = a.dense_region + 16ull * at;
-            if (threadIdx.x == 0) a.dense_off[i] = off;
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the flushes' stores have landed
-            const u32x4 *src = (const u32x4 *)(const void *)(a.out_base + a.out_off[i]);
-            u32x4 *dst = (u32x4 *)(void *)(a.dense + off);
-            for (uint32_t v0 = 0; v0 < nv; v0 += 256u) {
-                u32x4 t[4];
-#pragma unroll
-                for (uint32_t q = 0; q < 4u; ++q) {
-                    const uint32_t v = v0 + 64u * q + threadIdx.x;
-                    t[q] = __builtin_nontemporal_load(src + (v < nv ? v : nv - 1u));
-                }
-#pragma unroll
-                for (uint32_t q = 0; q < 4u; ++q) {
-                    const uint32_t v = v0 + 64u * q + threadIdx.x;
-                    if (v < nv) dst[v] = t[q];
-                }
-            }
-        }
-        __syncthreads();
-    }
+    typedef Decoder<RES_RING, false, true> Dec;
+    PZG_RESUME_WAVE(Dec);
+}
+// The gzip and the raw decoders (pzg_decoder_create_format).  Names of their own, and no template instances of the kernel above: the
+// zlib kernel stays the one kernel of its name in the code object.
+// (the gzip instance keeps the header's and the trailers' state beside the decoder's: at four waves per SIMD, 128 vector registers,
+// it spilled six of them -- 28 bytes of scratch per lane; three waves per SIMD, 168 registers, and nothing is spilled)
+#ifndef PZG_RES_GZIP_WAVES_PER_SIMD
+#define PZG_RES_GZIP_WAVES_PER_SIMD 3
+#endif
+__global__ __launch_bounds__(64, RES_RING == 15 ? 1 : PZG_RES_GZIP_WAVES_PER_SIMD) void resume_gzip_kernel(ResumeArgs a)
+{
+    typedef Decoder<RES_RING, true, true> Dec;
+    PZG_RESUME_WAVE(Dec);
+}
+__global__ __launch_bounds__(64, RES_RING == 15 ? 1 : PZG_RES_WAVES_PER_SIMD) void resume_raw_kernel(ResumeArgs a)
+{
+    typedef Decoder<RES_RING, false, true, true> Dec;
+    PZG_RESUME_WAVE(Dec);
 }
 
+static_assert(Decoder<RES_RING, true, true>::STRIP_WORDS == Decoder<RES_RING, false, true>::STRIP_WORDS &&
+              Decoder<RES_RING, false, true, true>::STRIP_WORDS == Decoder<RES_RING, false, true>::STRIP_WORDS, "one slice size for the three kernels");
 size_t resume_scalar_bytes() { return sizeof(ResumeState); }
 size_t resume_state_bytes() { return ResumeSlot<RES_RING>::BYTES; }
 
+static uint32_t resume_launch_waves_of(int num_cus, uint32_t n, uint32_t per_simd);
 size_t resume_strip_wave_bytes() { return (size_t)Decoder<RES_RING, false, true>::STRIP_WORDS * sizeof(uint32_t); }
-uint32_t resume_launch_waves(int num_cus, uint32_t n)
+uint32_t resume_launch_waves(int num_cus, uint32_t n) { return resume_launch_waves_of(num_cus, n, PZG_RES_WAVES_PER_SIMD); }
+static uint32_t resume_launch_waves_of(int num_cus, uint32_t n, uint32_t per_simd)
 {
     constexpr uint32_t by_lds = (160u * 1024u) / (uint32_t)((sizeof(WaveLds<RES_RING>) + 511u) / 512u * 512u);
-    constexpr uint32_t by_vgpr = RES_RING == 15 ? 4u : 4u * PZG_RES_WAVES_PER_SIMD;
+    const uint32_t by_vgpr = RES_RING == 15 ? 4u : 4u * per_simd;
     const uint32_t waves = (uint32_t)num_cus * (by_lds < by_vgpr ? by_lds : by_vgpr);
     return waves > n ? n : waves;
 }
 
-hipError_t launch_resume(const ResumeArgs &a, int num_cus, hipStream_t stream)
+hipError_t launch_resume(const ResumeArgs &a, uint32_t format, int num_cus, hipStream_t stream)
 {
     if (a.n == 0) return hipSuccess;
     hipError_t e = hipMemsetAsync(a.counter, 0, sizeof(uint32_t), stream);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(inflate_resume_kernel, dim3(resume_launch_waves(num_cus, a.n)), dim3(64), 0, stream, a);
-    return hipGetLastError();
+    const dim3 grid(resume_launch_waves_of(num_cus, a.n, format == RESUME_FORMAT_GZIP ? PZG_RES_GZIP_WAVES_PER_SIMD : PZG_RES_WAVES_PER_SIMD)), block(64);
+    if (format == RESUME_FORMAT_ZLIB)
+        hipLaunchKernelGGL(inflate_resume_kernel, grid, block, 0, stream, a);
+    else if (format == RESUME_FORMAT_GZIP)
+        hipLaunchKernelGGL(resume_gzip_kernel, grid, block, 0, stream, a);
+    else if (format == RESUME_FORMAT_RAW)
+        hipLaunchKernelGGL(resume_raw_kernel, grid, block, 0, stream, a);
+    else
+        return hipErrorInvalidValue;
+    e = hipGetLastError();
+    if (e != hipSuccess || format != RESUME_FORMAT_GZIP) return e;
+    return launch_resume_crc(a, num_cus, stream);  // the running CRC-32, before anything is downloaded
 }
 
 }  // namespace pzg

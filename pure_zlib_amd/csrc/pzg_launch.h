@@ -82,7 +82,11 @@ struct ResumeArgs {
     uint32_t *strip;
     uint32_t strip_waves;
 };
-hipError_t launch_resume(const ResumeArgs &a, int num_cus, hipStream_t stream);
+// format: RESUME_FORMAT_ZLIB -- zlib decoders (inflate_resume_kernel); RESUME_FORMAT_GZIP (PZG_GZIP) -- gzip decoders: resume_gzip_kernel,
+// then resume_crc_kernel over what they delivered; RESUME_FORMAT_RAW (PZG_RAW) -- raw decoders (resume_raw_kernel)
+constexpr uint32_t RESUME_FORMAT_ZLIB = 0u, RESUME_FORMAT_GZIP = 4u, RESUME_FORMAT_RAW = 32u;  // (pzg_api.cpp holds them against include/pzg.h)
+hipError_t launch_resume(const ResumeArgs &a, uint32_t format, int num_cus, hipStream_t stream);
+hipError_t launch_resume_crc(const ResumeArgs &a, int num_cus, hipStream_t stream);  // (pzg_kernels.hip, beside the batch CRC passes)
 size_t resume_state_bytes();   // one decoder's slot: ResumeState + LDS image
 size_t resume_scalar_bytes();  // ... its ResumeState part (zeroing it makes the decoder fresh)
 size_t resume_strip_wave_bytes();                      // one stream-wave's slice of ResumeArgs::strip

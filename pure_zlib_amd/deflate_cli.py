@@ -18,6 +18,10 @@ deflate --index foo.pzi --parallel foo.z               the same without the sequ
 deflate --use-index foo.pzi [--range OFF:LEN] foo.z    decodes foo with a wavefront per segment of the index and writes it; with
                                                        --range only the segments that cover LEN bytes from OFF, written to stdout
 
+Streaming mode for the other containers (on top of the reference): the same loop, the same messages, one resumable decoder
+deflate --gzip foo.gz                                  a gzip file (a series of members) -> foo
+deflate --raw foo.deflate                              a bare RFC 1951 stream -> foo (the name's last suffix is stripped)
+
 Members mode (pure_zlib_amd/gzfile.py), for a gzip file of MANY members -- BGZF, WARC, `cat a.gz b.gz`:
 deflate --members foo.gz                               finds the members on the device, decodes them with a wavefront per member in
                                                        one launch and writes foo; "ERROR: <show e>" for a file that does not decode
@@ -29,7 +33,8 @@ from .incremental import Chunk, DecompError, Done, NeedMore, decompress_incremen
 LAZY_CHUNK = 32 * 1024 - 16
 
 
-def run_decompression(out, chunks, decoder) -> None:
+def run_decompression(out, chunks, decoder, signal_end: bool = False) -> None:
+    """signal_end (--gzip, --raw): the last chunk is fed as the last one, so that a gzip decoder knows no further member follows."""
     while True:
         if isinstance(decoder, Done):
             if chunks:
@@ -40,7 +45,7 @@ def run_decompression(out, chunks, decoder) -> None:
             return
         if isinstance(decoder, NeedMore):
             if chunks:
-                decoder = decoder.feed(chunks.pop(0))
+                decoder = decoder.feed(chunks.pop(0), True) if signal_end and len(chunks) == 1 else decoder.feed(chunks.pop(0))
                 continue
             print("ERROR: Ran out of data mid-decompression.")
             return
@@ -143,8 +148,28 @@ def run_members(args) -> None:
         print("ERROR: " + r.value.show())
 
 
+def run_format(args, fmt) -> None:
+    """--gzip NAME.gz | --raw NAME.suffix: the streaming loop over one resumable decoder of that format."""
+    import os
+    if len(args) != 1:
+        print("USAGE: deflate --%s filename" % fmt)
+        return
+    target = args[0][:-3] if fmt == "gzip" and args[0].endswith(".gz") else os.path.splitext(args[0])[0] if fmt == "raw" else None
+    if not target or target == args[0]:
+        print("Unexpected file name.")
+        return
+    with open(args[0], "rb") as f:
+        data = f.read()
+    chunks = _lazy_chunks(data) or [b""]
+    with open(target, "wb") as out:
+        run_decompression(out, chunks, decompress_incremental(format=fmt), signal_end=True)
+
+
 def main(argv=None) -> int:
     args = sys.argv[1:] if argv is None else argv
+    if args and args[0] in ("--gzip", "--raw"):
+        run_format(args[1:], args[0][2:])
+        return 0
     if args and args[0] == "--many":
         run_many(args[1:])
         return 0

@@ -23,6 +23,7 @@ from .zlib import Context, DecompressionError, default_context, error_from_statu
 
 EXCESS_CHUNK = 32768  # OutputWindow.hs:42-43 excessChunkSize
 _ROOM = 256 * 1024    # output room per decoder and launch
+FORMATS = {"zlib": 0, "gzip": _ffi.GZIP, "raw": _ffi.RAW}  # pzg_decoder_create_format
 
 
 class Done:
@@ -55,23 +56,32 @@ class NeedMore:
     def __init__(self, pool: "DecoderPool", k: int):
         self._pool, self._k = pool, k
 
-    def feed(self, chunk: bytes):
-        """Apply the continuation to the next input chunk (Monad.hs:185-197 loadChunk)."""
-        return self._pool.feed([self._k], [chunk])[0]
+    def feed(self, chunk: bytes, final: bool = False):
+        """Apply the continuation to the next input chunk (Monad.hs:185-197 loadChunk).  final: no input follows this chunk (a gzip
+        decoder then knows that no further member does; running out of input becomes an error instead of NeedMore)."""
+        return self._pool.feed([self._k], [chunk], final)[0]
 
     def __repr__(self):
         return "NeedMore"
 
 
 class DecoderPool:
-    """n resumable zlib decoders on the device (pzg_decoder_create); feed() continues any subset of them in one launch."""
+    """n resumable decoders on the device (pzg_decoder_create_format); feed() continues any subset of them in one launch.
+    format: "zlib" (the reference's), "gzip" (a series of RFC 1952 members; CRC-32 and ISIZE are checked) or "raw" (bare RFC 1951,
+    nothing to check) -- all n decoders share it."""
 
-    def __init__(self, n: int, ctx: Optional[Context] = None, room: int = _ROOM):
+    def __init__(self, n: int, ctx: Optional[Context] = None, room: int = _ROOM, format: str = "zlib"):
+        if format not in FORMATS:
+            raise ValueError("format must be one of " + ", ".join(sorted(FORMATS)))
         self._ctx = ctx or default_context()
         self._L = _ffi.lib()
+        self.format = format
         import ctypes as C
         h = C.c_void_p()
-        _ffi.check(self._L.pzg_decoder_create(self._ctx.handle, n, C.byref(h)), self._ctx.handle)
+        if format == "zlib":
+            _ffi.check(self._L.pzg_decoder_create(self._ctx.handle, n, C.byref(h)), self._ctx.handle)
+        else:
+            _ffi.check(self._L.pzg_decoder_create_format(self._ctx.handle, n, FORMATS[format], C.byref(h)), self._ctx.handle)
         self._h = h
         self.n = n
         self._room = max(4096, int(room))
@@ -186,9 +196,9 @@ def _state_at(pool: "DecoderPool", k: int, events, i: int):
     return DecompError(e[1])
 
 
-def decompress_incremental(ctx: Optional[Context] = None):
-    """decompressIncremental: the initial decoder state (always NeedMore)."""
-    return DecoderPool(1, ctx).start(0)
+def decompress_incremental(ctx: Optional[Context] = None, format: str = "zlib"):
+    """decompressIncremental: the initial decoder state (always NeedMore).  format: "zlib" (the reference's), "gzip" or "raw"."""
+    return DecoderPool(1, ctx, format=format).start(0)
 
 
 decompressIncremental = decompress_incremental
