@@ -241,6 +241,7 @@ PZG_API void  pzg_host_free(void *p);
  *   detail[2n]             two detail words per stream (see the status table); may be NULL
  *   in_used[n]             input bytes consumed incl. the Adler trailer; may be NULL
  *   adler[n]               Adler-32 computed over the decoded bytes; may be NULL.  With PZG_GZIP: the CRC-32 of them.
+ *                          0 for PZG_E_OUT_TOO_SMALL: nothing of such a stream is delivered.
  * (PZG_RAW: bare RFC 1951 streams instead, see the flag; with PZG_CRC32 adler[] holds their CRC-32.)
  *
  * A stream that FAILED (status neither PZG_OK nor PZG_E_OUT_TOO_SMALL) delivers what the reference had emitted before the error:

@@ -76,7 +76,7 @@
 
 // Lab build of the HOST model only (-DPZG_STATS, tests/tools/model_stats.py): event counts of the token loop
 #if defined(PZG_STATS) && !PZG_DEVICE_PASS
-struct PzgStats { unsigned long long v[32]; };
+struct PzgStats { unsigned long long v[40]; };
 extern PzgStats pzg_stats;
 #define PZG_STAT(i, n) (pzg_stats.v[i] += (unsigned long long)(n))
 #else
@@ -1893,6 +1893,7 @@ struct Decoder {
             const uint64_t first = stopmask & (0ull - stopmask);
             PZG_STAT(4, (first & lanes_ballot(BIG)) ? 1 : 0);  // ended by the 128-byte limit
             PZG_STAT(5, (!(first & lanes_ballot(BIG)) && (first & lanes_ballot(SRC_IN))) ? 1 : 0);  // ... by a source inside the segment
+            PZG_STAT(32, (first & lanes_ballot(MATCH) & lanes_ballot(SRC_OUT)) ? 1 : 0);  // ... by a match whose source lies before the output and its history
         } else {
             PZG_STAT(6, 1);  // the queue ran out
         }
@@ -3453,6 +3454,13 @@ struct Decoder {
         const uint64_t stopm = lanes_ballot(OVER) | (lanes_ballot(HASM) & (lanes_ballot(BAD) | (RING_BITS == 15 ? lanes_ballot(MIX) : 0ull)));
         const uint32_t v0 = stopm ? ctz64(stopm) : n;
         const uint32_t v = v0 < n ? v0 : n;  // sequences of this group
+#if defined(PZG_STATS) && !PZG_DEVICE_PASS
+        if (v0 < n) {  // what stopped the group: the first sequence that is not part of it
+            const uint64_t first = stopm & (0ull - stopm), m_bad = first & lanes_ballot(HASM) & lanes_ballot(BAD);
+            PZG_STAT(33, m_bad ? 1 : 0);  // ... a match that reaches in front of the output and its history
+            PZG_STAT(34, (RING_BITS == 15 && !m_bad && !(first & lanes_ballot(OVER)) && (first & lanes_ballot(HASM) & lanes_ballot(MIX))) ? 1 : 0);  // ... MIX alone
+        }
+#endif
         if (__builtin_expect(v == 0u, 0)) return SQ_SOLO;
         const uint32_t endv = lane_get(ENDX, v - 1u), run = endv & 0xffffu, lend_v = endv >> 16;
         const uint64_t taken = v >= 64u ? ~0ull : bit_field_mask(v, 0u);
@@ -3834,7 +3842,8 @@ struct Decoder {
     // The record at the head of the span on its own: its literals by all lanes (64 bytes a step), its match by copy_match().
     PZG_FN int seq_solo()
     {
-        PZG_STAT(24, 1);
+        PZG_STAT(24, 1);  // (with the long matches that seq_group copies by all lanes: what tests/tools/model_stats.py reports per group)
+        PZG_STAT(35, 1);  // solo sequences alone: a stream's way through seq_solo, which the tests of the history's edges assert
         maybe_flush();
         const uint32_t rec = lane_get(QTN, 0u), nl = seq_nl(rec), len = seq_len(rec), dist = seq_dist(rec);
         const uint32_t lit_a = reg_lit(lane_get(QINFO, 0u) & 255u) + s_lc;
@@ -4246,8 +4255,9 @@ struct Decoder {
         res->detail0 = detail0;
         res->detail1 = detail1;
         // (a stream that FAILED after it had outgrown its capacity: what lies past the capacity was never stored, on the small rings
-        // the far reads of it were skipped, so the running checksum means nothing -- and must not depend on what the wave decoded before)
-        const bool unstored = op > cap && status != ST_OK && status != ST_OUT_TOO_SMALL && status != ST_RETRY_FULL_RING;
+        // the far reads of it were skipped, so the running checksum means nothing -- and must not depend on what the wave decoded before.
+        // ST_OUT_TOO_SMALL alike: adler[] is the checksum of the bytes DELIVERED, and a stream that outgrew its capacity delivers none)
+        const bool unstored = op > cap && status != ST_OK && status != ST_RETRY_FULL_RING;
         res->adler = unstored ? 0u : (adler_b << 16) | adler_a;
         res->gz_crc = gz_expect;
         res->out_len = op;
