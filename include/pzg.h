@@ -386,6 +386,35 @@ PZG_API int pzg_index_scan(pzg_ctx *ctx, const uint8_t *in, uint64_t in_len,
         uint64_t *out_len, int32_t *status, uint32_t detail[2], uint64_t *in_used,
         uint32_t flags);  /* 0 or PZG_DEVICE_PTRS */
 
+/*
+ * pzg_index_scan_many (0.5): pzg_index_scan over n raw streams in ONE call -- the large members of a gzip file or a ZIP archive, each
+ * too few chunks to fill the chip alone.  The chunks of all streams form one list: a wavefront per chunk finds and decodes as above
+ * (it finds its stream by a binary search over the streams' first chunks), a workgroup per stream walks that stream's chain.
+ * Stream s is in_base + in_off[s] .. + in_len[s]; it owns the point and window slots point_off[s] .. point_off[s + 1] (point_off:
+ * n + 1 entries, ascending; windows: point_off[n] x 32768 bytes, or NULL).  For every stream, points, windows (the window at the END
+ * of its slot, the front of the slot untouched), npoints[s] (the count the stream HAS), out_len[s], in_used[s], status[s] (PZG_OK or
+ * PZG_E_SCAN) and detail[2s], detail[2s + 1] are exactly what pzg_index_scan gives for that stream alone with the same chunk and span
+ * and max_points = point_off[s + 1] - point_off[s]: chunks are cut per stream from the stream's own first byte, and a broken stream
+ * changes nothing in its neighbours' results or slots.
+ * flags: 0 -- in_base, points and windows are host memory; PZG_DEVICE_PTRS -- they are device memory.  in_off, in_len, point_off and
+ * every result array are host memory in both forms (the host sizes the grid by the chunk counts), and the call returns when the
+ * results are in place: it runs on a stream of the library's own.  PZG_RC_BAD_ARG: n == 0; any other flag (PZG_RAW is implied); a
+ * context of several devices; chunk non-zero and below 256; an in_len[s] of 2^34 or more; an in_off[s] above 2^62; descending
+ * point_off; more than 2^32 - 1 chunks in total.  Nothing is read but the aligned dwords that hold a stream's bytes.
+ * Device memory: 64 KiB + 32 bytes per chunk plus 64 KiB + 256 bytes per stream, allocated for the call and freed before it returns;
+ * PZG_RC_NO_MEMORY when the device does not have it.  The host-pointer form also stages the input -- from the first stream's first
+ * byte to the last one's last, in one piece -- and the slots in the context's arenas.
+ */
+PZG_API int pzg_index_scan_many(pzg_ctx *ctx,
+        const uint8_t *in_base, const uint64_t *in_off, const uint64_t *in_len, uint32_t n,
+        uint64_t chunk, uint64_t span,                           /* as for pzg_index_scan */
+        pzg_index_point *points, const uint32_t *point_off,      /* n + 1, ascending */
+        uint32_t *npoints,                                       /* n */
+        uint8_t *windows,                                        /* point_off[n] x 32768 bytes, or NULL */
+        uint64_t *out_len, int32_t *status, uint32_t *detail,    /* detail: 2n, or NULL */
+        uint64_t *in_used,                                       /* n, or NULL */
+        uint32_t flags);                                         /* 0 or PZG_DEVICE_PTRS */
+
 PZG_API int pzg_decompress_many_segments(pzg_ctx *ctx,
         const uint8_t *in_base, const uint64_t *in_off, const uint64_t *in_len,
         const uint8_t *start_bit, const uint64_t *end_bit,
@@ -424,7 +453,8 @@ PZG_API int pzg_decompress_many_segments(pzg_ctx *ctx,
  * Device memory, allocated for the call and freed before it returns: find -- 8 bytes per chunk (+ 8 per 4,096 chunks); layout -- 8
  * bytes per 4,096 members.  The host-pointer forms also stage the input and the arrays in the context's arenas (in_len + 12 bytes
  * per max_members; in_len + 40 bytes per member), which the context keeps.  PZG_RC_NO_MEMORY when the device does not have it.
- * Not done here: a single member is still one wavefront's work (splitting a huge one with pzg_index_scan is up to the caller).
+ * A single member is one wavefront's work in these calls: a caller splits the large ones with pzg_index_scan_many and decodes their
+ * segments with pzg_decompress_many_segments (the Python mirror's decompress_gzip_file and read_zip do).
  */
 PZG_API int pzg_gzip_find_members(pzg_ctx *ctx, const uint8_t *in, uint64_t in_len,
         uint64_t chunk,                  /* 0: 64 KiB; below 64: PZG_RC_BAD_ARG */

@@ -45,6 +45,7 @@
 #include "../../include/pzg.h"
 #include "pzg_helpers.h"
 #include "pzg_launch.h"
+#include "scan_core.h"  // (ScanStream, ScanResult: the tables of pzg_index_scan_many)
 
 namespace {
 
@@ -1565,6 +1566,106 @@ int pzg_index_scan(pzg_ctx *ctx, const uint8_t *in, uint64_t in_len, uint64_t ch
             const size_t np = r.npoints < max_points ? r.npoints : max_points;
             if (np) HIP_TRY(ctx, hipMemcpy(points, d_pts, 16 * np, hipMemcpyDeviceToHost));
             if (np && windows) return copy_back_windows(ctx, points, np, windows, d_win);
+        }
+        return PZG_RC_OK;
+    });
+}
+
+int pzg_index_scan_many(pzg_ctx *ctx, const uint8_t *in_base, const uint64_t *in_off, const uint64_t *in_len, uint32_t n, uint64_t chunk, uint64_t span,
+                        pzg_index_point *points, const uint32_t *point_off, uint32_t *npoints, uint8_t *windows, uint64_t *out_len, int32_t *status,
+                        uint32_t *detail, uint64_t *in_used, uint32_t flags)
+{
+    if (!ctx_live(ctx)) return PZG_RC_BAD_ARG;
+    if (flags & ~(PZG_DEVICE_PTRS | PZG_RAW)) return PZG_RC_BAD_ARG;  // (PZG_RAW is implied, as for pzg_index_scan)
+    if (ctx->shards.size() != 1) return PZG_RC_BAD_ARG;
+    if (n == 0 || !in_base || !in_off || !in_len || !point_off || !npoints || !out_len || !status) return PZG_RC_BAD_ARG;
+    if (chunk == 0) chunk = 128u << 10;
+    if (chunk < 256u) return PZG_RC_BAD_ARG;
+    if (span == 0) span = 1ull << 20;
+    // the tables of the launch (declared before the LaneCall below: its copies read them): the streams, then first_chunk
+    uint64_t lo = ~0ull, hi = 0, nchunks64 = 0;
+    for (uint32_t s = 0; s < n; ++s) {
+        if ((in_len[s] >> 34) || in_off[s] > (1ull << 62) || point_off[s + 1] < point_off[s]) return PZG_RC_BAD_ARG;
+        nchunks64 += in_len[s] ? (in_len[s] + chunk - 1u) / chunk : 1u;
+        if (nchunks64 > 0xffffffffull) return PZG_RC_BAD_ARG;
+        lo = in_off[s] < lo ? in_off[s] : lo;
+        hi = in_off[s] + in_len[s] > hi ? in_off[s] + in_len[s] : hi;
+    }
+    const uint32_t slots = point_off[n];
+    if (slots > point_off[0] && !points) return PZG_RC_BAD_ARG;
+    const bool dev = (flags & PZG_DEVICE_PTRS) != 0;
+    return guarded(ctx, "pzg_index_scan_many", [&]() -> int {
+        Shard &sh = *ctx->shards[0];
+        const size_t table_bytes = pzg::scan_many_table_bytes(n);
+        std::vector<uint64_t> table((table_bytes + 7u) / 8u, 0u);
+        std::vector<pzg::ScanResult> res(n);
+        std::vector<pzg_index_point> pts;
+        CallScratch scratch;
+        LaneCall call(ctx, sh);
+        if (call.rc != PZG_RC_OK) return call.rc;
+        Lane &ln = call.ln;
+        hipStream_t st = call.st;
+        // host pointers: the bytes from the first stream's first to the last one's last travel in one piece, the streams stay where
+        // they are inside it
+        const uint64_t bias = dev ? 0u : lo;
+        const uint8_t *d_in = nullptr;
+        uint8_t *d_win = windows;
+        uint64_t *d_pts = (uint64_t *)points;
+        const size_t win_off = pad256(16 * (size_t)slots);
+        int rc;
+        if (!dev) {
+            if ((rc = arena_reserve(ctx, ln.d_out[0], win_off + (windows ? 32768 * (size_t)slots : 0) + 64)) != PZG_RC_OK) return rc;
+            d_pts = (uint64_t *)ln.d_out[0].p;
+            d_win = windows ? (uint8_t *)ln.d_out[0].p + win_off : nullptr;
+        }
+        if ((rc = stage_input(call, in_base + bias, dev ? 0u : hi - lo, dev, d_in)) != PZG_RC_OK) return rc;
+        if ((rc = scratch.reserve(pzg::scan_many_scratch_bytes(n, (uint32_t)nchunks64))) != PZG_RC_OK) return rc;
+        pzg::ScanStream *hs = (pzg::ScanStream *)(void *)table.data();
+        uint32_t *first_chunk = (uint32_t *)(void *)(hs + n);
+        uint32_t at = 0;
+        for (uint32_t s = 0; s < n; ++s) {
+            hs[s] = pzg::ScanStream{in_off[s] - bias, in_len[s], point_off[s], d_pts ? point_off[s + 1] - point_off[s] : 0u, 0u};
+            first_chunk[s] = at;
+            at += in_len[s] ? (uint32_t)((in_len[s] + chunk - 1u) / chunk) : 1u;
+        }
+        first_chunk[n] = at;
+        pzg::ScanManyArgs a{};
+        a.in_base = d_in;
+        a.chunk = chunk;
+        a.span = span;
+        a.n = n;
+        a.nchunks = at;
+        a.points = d_pts;
+        a.windows = d_win;
+        pzg::scan_many_layout(a, (uint8_t *)scratch.p);
+        HIP_TRY(ctx, hipMemcpyAsync(a.streams, table.data(), table_bytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, call.begin_timed());
+        HIP_TRY(ctx, pzg::launch_scan_many(a, st));
+        HIP_TRY(ctx, call.end_timed());
+        HIP_TRY(ctx, hipMemcpyAsync(res.data(), a.results, sizeof(pzg::ScanResult) * (size_t)n, hipMemcpyDeviceToHost, st));
+        if ((rc = call.finish()) != PZG_RC_OK) return rc;
+        bool any = false;
+        for (uint32_t s = 0; s < n; ++s) {
+            const pzg::ScanResult &r = res[s];
+            out_len[s] = r.out_len;
+            status[s] = r.status;
+            npoints[s] = r.npoints;
+            if (in_used) in_used[s] = r.in_used;
+            if (detail) {
+                detail[2 * (size_t)s] = r.d0;
+                detail[2 * (size_t)s + 1] = r.d1;
+            }
+            any = any || (r.status == 0 && r.npoints && point_off[s + 1] > point_off[s]);
+        }
+        if (!dev && any) {  // every slot's points in one copy, then each sound stream's own to the caller, and its windows
+            pts.resize(slots);
+            HIP_TRY(ctx, hipMemcpy(pts.data(), d_pts, 16 * (size_t)slots, hipMemcpyDeviceToHost));
+            for (uint32_t s = 0; s < n; ++s) {
+                const size_t room = point_off[s + 1] - point_off[s], np = res[s].npoints < room ? res[s].npoints : room, o = point_off[s];
+                if (res[s].status != 0 || np == 0) continue;
+                memcpy(points + o, pts.data() + o, 16 * np);
+                if (windows && (rc = copy_back_windows(ctx, points + o, np, windows + 32768 * o, d_win + 32768 * o)) != PZG_RC_OK) return rc;
+            }
         }
         return PZG_RC_OK;
     });

@@ -5,6 +5,7 @@
 //   inflate_raw_kernel<RB, *>       the raw instances
 //   inflate_seg_kernel              the segment instance (indexed streams), and index_windows_kernel beside it
 //   scan_find / scan_decode / scan_resolve_kernel   the parallel index scan (scan_core.h)
+//   scan_many_find / _decode / _resolve_kernel      the same over many streams in one launch (scan_core.h ScanMany)
 //   member_* / sums_*_kernel        the members of a gzip file, found and laid out (member_core.h)
 //
 // SDWA forms save a vector instruction here and there (an extract folded into an add) but take their operands from registers
@@ -227,6 +228,66 @@ hipError_t launch_scan(ScanArgs a, uint8_t *scratch, hipStream_t stream)
     hipLaunchKernelGGL(scan_find_kernel, dim3(a.nchunks), dim3(64), 0, stream, a);
     hipLaunchKernelGGL(scan_decode_kernel, dim3(a.nchunks), dim3(64), 0, stream, a);
     hipLaunchKernelGGL(scan_resolve_kernel, dim3(1), dim3(1024), 0, stream, a);
+    return hipGetLastError();
+}
+
+// ... of many streams in one launch (pzg_index_scan_many; scan_core.h ScanMany): the same three passes over the chunks of all streams
+// as one list -- a wave finds its stream by a binary search over first_chunk -- and a workgroup per stream for the walk.
+__global__ __launch_bounds__(64) void scan_many_find_kernel(ScanManyArgs a)
+{
+    __shared__ ScanLds lds;
+    if (blockIdx.x >= a.nchunks) return;
+    ScanMany::find(lds, a.in_base, a.streams, a.first_chunk, a.n, a.chunk, blockIdx.x, a.cand);
+}
+
+__global__ __launch_bounds__(64) void scan_many_decode_kernel(ScanManyArgs a)
+{
+    __shared__ ScanLds lds;
+    if (blockIdx.x >= a.nchunks) return;
+    ScanMany::decode(lds, a.in_base, a.streams, a.first_chunk, a.n, blockIdx.x, a.cand, a.rings, a.next, a.count, a.endbit);
+}
+
+__global__ __launch_bounds__(1024) void scan_many_resolve_kernel(ScanManyArgs a)
+{
+    if (blockIdx.x >= a.n) return;
+    ScanMany::resolve(threadIdx.x, blockDim.x, a.streams, a.first_chunk, blockIdx.x, a.cand, a.next, a.count, a.endbit, a.rings, a.span, a.wbuf,
+                      a.points, a.windows, a.results);
+}
+
+// the tables the host uploads in one piece: n stream entries, then first_chunk (n + 1 entries), padded to the results' alignment
+size_t scan_many_table_bytes(uint32_t n) { return sizeof(ScanStream) * (size_t)n + ((4u * ((size_t)n + 1u) + 7u) & ~(size_t)7u); }
+
+size_t scan_many_scratch_bytes(uint32_t n, uint32_t nchunks)
+{
+    // per chunk: the ring (64 KiB) and 32 bytes -- cand, count, endbit (8 each), next (4), 4 to spare; per stream: the chain walk's two
+    // windows (64 KiB) and 256 bytes -- its entry (32), its result (32), its first_chunk (4, and 4 of the table's last entry), the
+    // rest to spare: the figure include/pzg.h documents
+    return (size_t)nchunks * (2u * Scan::RING + 32u) + (size_t)n * (2u * Scan::RING + 256u);
+}
+
+void scan_many_layout(ScanManyArgs &a, uint8_t *scratch)
+{
+    static_assert(sizeof(ScanStream) == 32 && sizeof(ScanResult) == 32, "the per-stream entries");
+    const size_t nc = a.nchunks, n = a.n;
+    a.rings = (uint16_t *)(void *)scratch;
+    uint8_t *p = scratch + nc * 2u * Scan::RING;
+    a.wbuf = p;
+    p += n * 2u * Scan::RING;
+    a.cand = (uint64_t *)(void *)p;
+    a.count = a.cand + nc;
+    a.endbit = a.count + nc;
+    a.next = (uint32_t *)(void *)(a.endbit + nc);
+    p += 32u * nc;
+    a.streams = (ScanStream *)(void *)p;
+    a.first_chunk = (uint32_t *)(void *)(a.streams + n);
+    a.results = (ScanResult *)(void *)(p + scan_many_table_bytes(a.n));
+}
+
+hipError_t launch_scan_many(const ScanManyArgs &a, hipStream_t stream)
+{
+    hipLaunchKernelGGL(scan_many_find_kernel, dim3(a.nchunks), dim3(64), 0, stream, a);
+    hipLaunchKernelGGL(scan_many_decode_kernel, dim3(a.nchunks), dim3(64), 0, stream, a);
+    hipLaunchKernelGGL(scan_many_resolve_kernel, dim3(a.n), dim3(1024), 0, stream, a);
     return hipGetLastError();
 }
 

@@ -130,6 +130,32 @@ struct ScanArgs {
 size_t scan_scratch_bytes(uint32_t nchunks);
 hipError_t launch_scan(ScanArgs a, uint8_t *scratch, hipStream_t stream);
 
+// ... of many streams in one launch (pzg_index_scan_many): a wave per chunk of ALL streams, a workgroup per stream for the walk.
+// scan_many_layout() lays out what is below the line in `scratch` (scan_many_scratch_bytes(n, nchunks) bytes, 256-byte aligned).
+// The caller then copies the n stream entries and, behind them, the n + 1 entries of first_chunk to a.streams in one piece
+// (scan_many_table_bytes(n) bytes) on the stream it launches on; launch_scan_many() enqueues the three kernels; the results are at
+// a.results.
+struct ScanStream;
+struct ScanManyArgs {
+    const uint8_t *in_base;
+    uint64_t chunk, span;
+    uint32_t n, nchunks;  // streams; chunks of all of them
+    uint64_t *points;     // {in_bit, out_pos} pairs: stream s at its point_off
+    uint8_t *windows;     // 32768 bytes per point slot, or null
+    // ----
+    ScanStream *streams;
+    uint32_t *first_chunk;
+    ScanResult *results;
+    uint64_t *cand, *count, *endbit;
+    uint32_t *next;
+    uint16_t *rings;
+    uint8_t *wbuf;
+};
+size_t scan_many_scratch_bytes(uint32_t n, uint32_t nchunks);
+size_t scan_many_table_bytes(uint32_t n);
+void scan_many_layout(ScanManyArgs &a, uint8_t *scratch);
+hipError_t launch_scan_many(const ScanManyArgs &a, hipStream_t stream);
+
 // the members of a gzip file (pzg_kernels_b.hip, member_core.h).  The caller fills in what is above the line; `scratch`:
 // members_find_scratch_bytes(nchunks) bytes of device memory, 8-byte aligned; the count of candidates lands at members_find_total().
 struct MemberArgs {

@@ -504,4 +504,87 @@ struct Scan {
     }
 };
 
+// ---- many streams in one launch (pzg_index_scan_many) ----------------------------------------------------------------------------
+// The chunks of all streams form ONE list, stream after stream: stream s owns entries first_chunk[s] .. first_chunk[s + 1] of cand,
+// next, count, endbit and rings, cut from its own first byte, and slot s of the walk's windows and of the results.  A wave (find,
+// decode) or a workgroup (resolve) finds its stream and hands that stream's slices to Scan's three passes as they are: to them
+// every stream is the only one.
+struct ScanStream {
+    uint64_t in_off, in_len;         // the stream: in_base + in_off .. + in_len
+    uint32_t point_off, max_points;  // its slots of points and windows: point_off .. + max_points
+    uint64_t reserved;
+};
+
+struct ScanMany {
+    // The stream that owns entry g of the list: the last s with first_chunk[s] <= g.  first_chunk: n + 1 entries, ascending,
+    // first_chunk[0] = 0 and g < first_chunk[n]; a stream without chunks (two equal entries) owns nothing.  Wave-uniform.
+    PZG_FN static uint32_t locate(const uint32_t *first_chunk, uint32_t n, uint32_t g)
+    {
+        uint32_t lo = 0, hi = n;  // first_chunk[lo] <= g < first_chunk[hi]
+        while (hi - lo > 1u) {
+            const uint32_t mid = lo + ((hi - lo) >> 1);
+            if (uni(first_chunk[mid]) <= g) lo = mid;
+            else hi = mid;
+        }
+        return lo;
+    }
+
+    // the input of one stream as Scan reads it: the aligned dwords that hold its bytes, the stream's bit 0 at bit mis_bits of src[0]
+    struct Input {
+        const uint32_t *src;
+        uint64_t ndw, end_bit, in_len;
+        uint32_t mis_bits;
+    };
+    PZG_FN static Input input(const uint8_t *in_base, const ScanStream &st)
+    {
+        const uint8_t *in = in_base + uni64(st.in_off);
+        const uint32_t mis = (uint32_t)((uintptr_t)in & 3u);
+        Input I;
+        I.in_len = uni64(st.in_len);
+        I.src = (const uint32_t *)(const void *)(in - mis);
+        I.ndw = (mis + I.in_len + 3u) >> 2;
+        I.mis_bits = 8u * mis;
+        I.end_bit = 8u * (mis + I.in_len);
+        return I;
+    }
+
+    // entry g of the list: the candidate of that chunk of its stream (its chunk 0: bit 0)
+    PZG_FN static void find(ScanLds &L, const uint8_t *in_base, const ScanStream *streams, const uint32_t *first_chunk, uint32_t n,
+                            uint64_t chunk, uint32_t g, uint64_t *cand)
+    {
+        const uint32_t s = locate(first_chunk, n, g), k = g - uni(first_chunk[s]);
+        uint64_t q = 0;
+        if (k) {
+            const Input I = input(in_base, streams[s]);
+            const uint64_t from = 8u * (uint64_t)k * chunk, all = 8u * I.in_len;
+            const uint64_t to = from + 8u * chunk < all ? from + 8u * chunk : all;
+            q = Scan::find(L, I.src, I.ndw, I.end_bit, from + I.mis_bits, to + I.mis_bits);
+            if (q != Scan::NONE) q -= I.mis_bits;
+        }
+        if (lane_id() == 0) cand[g] = q;
+    }
+
+    // entry g of the list: the segment from that chunk's candidate, over its stream's candidates alone
+    PZG_FN static void decode(ScanLds &L, const uint8_t *in_base, const ScanStream *streams, const uint32_t *first_chunk, uint32_t n,
+                              uint32_t g, const uint64_t *cand, uint16_t *rings, uint32_t *next, uint64_t *count, uint64_t *endbit)
+    {
+        const uint32_t s = locate(first_chunk, n, g), base = uni(first_chunk[s]), nk = uni(first_chunk[s + 1u]) - base;
+        const Input I = input(in_base, streams[s]);
+        Scan::decode(L, I.src, I.ndw, I.mis_bits, I.end_bit, cand + base, nk, g - base, rings + (size_t)g * Scan::RING, next + base,
+                     count + base, endbit + base);
+    }
+
+    // stream s: its chain, its points and windows into its own slots, its result.  wbufs: 2 x 32768 bytes per stream.
+    PZG_FN static void resolve(uint32_t tid, uint32_t nt, const ScanStream *streams, const uint32_t *first_chunk, uint32_t s,
+                               const uint64_t *cand, const uint32_t *next, const uint64_t *count, const uint64_t *endbit,
+                               const uint16_t *rings, uint64_t span, uint8_t *wbufs, uint64_t *points, uint8_t *windows, ScanResult *results)
+    {
+        const uint32_t base = first_chunk[s], nk = first_chunk[s + 1u] - base;
+        const size_t slot = streams[s].point_off;
+        Scan::resolve(tid, nt, cand + base, next + base, count + base, endbit + base, rings + (size_t)base * Scan::RING, nk, span,
+                      wbufs + (size_t)s * 2u * Scan::RING, points + 2u * slot, streams[s].max_points,
+                      windows ? windows + slot * Scan::RING : nullptr, results + s);
+    }
+};
+
 }  // namespace pzg

@@ -25,6 +25,8 @@ deflate --raw foo.deflate                              a bare RFC 1951 stream ->
 Members mode (pure_zlib_amd/gzfile.py), for a gzip file of MANY members -- BGZF, WARC, `cat a.gz b.gz`:
 deflate --members foo.gz                               finds the members on the device, decodes them with a wavefront per member in
                                                        one launch and writes foo; "ERROR: <show e>" for a file that does not decode
+deflate --members --split BYTES foo.gz                 the same; members of BYTES compressed bytes or more are split over many
+                                                       wavefronts each (pure_zlib_amd/split.py; 0: none)
 """
 import sys
 
@@ -131,16 +133,22 @@ def run_indexed(args) -> None:
 
 
 def run_members(args) -> None:
-    """Members mode: --members NAME.gz."""
+    """Members mode: --members [--split BYTES] NAME.gz."""
     from .gzfile import decompress_gzip_file
+    args, split = list(args), None
+    if "--split" in args:  # (in front of the name or behind it)
+        at = args.index("--split")
+        if at + 1 < len(args) and args[at + 1].isdigit():
+            split = int(args[at + 1])
+            del args[at:at + 2]
     if len(args) != 1:
-        print("USAGE: deflate --members filename")
+        print("USAGE: deflate --members [--split BYTES] filename")
         return
     if not args[0].endswith(".gz"):
         print("Unexpected file name.")
         return
     with open(args[0], "rb") as f:
-        r = decompress_gzip_file(f.read())
+        r = decompress_gzip_file(f.read(), split=split)
     if r.is_right():
         with open(args[0][:-3], "wb") as out:
             out.write(r.value)

@@ -17,8 +17,13 @@ or went on, the rest of the file goes to the one-stream decode, which does the s
 members from j on are laid out and decoded again.  Beyond MAX_DROPS drops in a row for one member or MAX_REPAIRS repair launches the
 whole file goes to the one-stream decode, whose result -- and error text -- is then the file's.
 
-Limits: a single member is still one wavefront's work (splitting a huge one with pzg_index_scan is not done here), and a member
-of 4 GiB or more, whose ISIZE has wrapped, ends in the one-stream decode.
+A LARGE member (decompress_gzip_file's `split`: that many compressed bytes or more) is not left to one wavefront: the large members
+of a launch are scanned in one call (pzg_index_scan_many) and their segments decoded in one launch, straight into their places
+(pure_zlib_amd/split.py).  Only a member whose size and CRC-32 come out as its trailer says is taken from that; every other one is
+decoded by the gzip launch as before, so the acceptance chain, the repairs and every error text are untouched.
+
+Limits: a member of 4 GiB or more, whose ISIZE has wrapped, ends in the one-stream decode; MemberIndex.read() decodes a member it
+touches on one wavefront, however large.
 """
 import ctypes as C
 from typing import List, Optional, Tuple
@@ -26,8 +31,9 @@ from typing import List, Optional, Tuple
 import numpy as np
 
 from . import _ffi
+from . import split as _split
 from . import zlib as _z
-from .indexed import _fingerprint
+from .indexed import _fingerprint, parse_gzip_header
 from .zlib import Context, DecompressionError_, Either, Left, Right, default_context, error_from_status
 
 MAX_DROPS = 4     # candidates dropped in a row behind one member
@@ -78,18 +84,66 @@ def layout(buf: np.ndarray, n: int, starts, ctx: Context):
     return (*arrays, int(total.value))
 
 
-def _launch(buf, in_off, in_len, out_off, out_cap, total, ctx):
-    """The members in ONE PZG_GZIP launch: (out, out_len, status, detail, in_used)."""
+def _launch(buf, in_off, in_len, out_off, out_cap, total, ctx, split=0, split_chunk=None):
+    """The members in ONE PZG_GZIP launch: (out, out_len, status, detail, in_used).  split: the members of that many bytes or more go
+    to split.split_decode first, many wavefronts each; one that comes back verified is filled in as the gzip kernel would have
+    filled it in, every other one is decoded by the launch with the rest."""
     out = np.empty(total + 16, dtype=np.uint8)
-    out_len, status, detail, in_used, _crc = ctx.decompress_many_raw(buf, in_off, in_len, out, out_off, out_cap, gzip=True)
+    m = len(in_off)
+    rest = np.arange(m)
+    bodies, which = [], []
+    if split:
+        for j in np.flatnonzero(in_len >= split).tolist():
+            body = _large_body(buf, int(in_off[j]), int(in_len[j]), int(out_off[j]), int(out_cap[j]))
+            if body is not None:
+                bodies.append(body)
+                which.append(j)
+    if not bodies:
+        out_len, status, detail, in_used, _crc = ctx.decompress_many_raw(buf, in_off, in_len, out, out_off, out_cap, gzip=True)
+        return out, out_len, status, detail, in_used
+    done = _split.split_decode(buf, bodies, out, ctx, split_chunk)
+    taken = np.array([j for j, ok in zip(which, done) if ok], dtype=np.int64)
+    rest = np.setdiff1d(rest, taken)
+    out_len, status = np.zeros(m, dtype=np.uint64), np.full(m, -1, dtype=np.int32)
+    detail, in_used = np.zeros((m, 2), dtype=np.uint32), np.zeros(m, dtype=np.uint64)
+    out_len[taken], status[taken], in_used[taken] = out_cap[taken], _ffi.OK, in_len[taken]
+    out_len[rest], status[rest], detail[rest], in_used[rest], _crc = ctx.decompress_many_raw(
+        buf, in_off[rest], in_len[rest], out, out_off[rest], out_cap[rest], gzip=True)
     return out, out_len, status, detail, in_used
 
 
-def decompress_gzip_file(data, ctx: Optional[Context] = None, chunk: Optional[int] = None, return_index: bool = False):
+def _large_body(buf, off, length, out_off, out_cap):
+    """The raw body of the member buf[off : off + length] as a split.Body, its size and CRC-32 from the trailer; None when the extent
+    does not read as header | body | trailer, or its ISIZE is more than the room the layout gave it (no sound member's is)."""
+    extent = buf[off:off + length]
+    try:  # (a header longer than this reads as cut short: such a member is not split)
+        h = parse_gzip_header(extent[:1 << 17].tobytes())
+    except _z.DecompressionError:
+        return None
+    if length < h + 8:
+        return None
+    crc = int.from_bytes(extent[length - 8:length - 4].tobytes(), "little")
+    isize = int.from_bytes(extent[length - 4:].tobytes(), "little")
+    if isize != out_cap:
+        return None
+    return _split.Body(off + h, length - h - 8, isize, crc, out_off)
+
+
+def decompress_gzip_file(data, ctx: Optional[Context] = None, chunk: Optional[int] = None, return_index: bool = False,
+                         split: Optional[int] = None, split_chunk: Optional[int] = None):
     """The members of a gzip file decoded in parallel.  Returns what gzip_decompress_many([data])[0] returns -- the same bytes for a
-    Right, the same show() text for a Left -- or, with return_index, (MemberIndex or None, that)."""
+    Right, the same show() text for a Left -- or, with return_index, (MemberIndex or None, that).
+    split: members of that many compressed bytes or more are decoded by many wavefronts each (pure_zlib_amd.split; split_chunk: the
+    compressed bytes per wavefront of their scan); None: split.DEFAULT_SPLIT; 0: none, every member is one wavefront's work.  Only
+    the time depends on it.  The MemberIndex does not record the split: index.read() of a range inside a large member still decodes
+    that member on one wavefront."""
     if chunk is not None and chunk < 64:
         raise ValueError("chunk must be 64 or more")
+    if split_chunk is not None and split_chunk < 256:
+        raise ValueError("split_chunk must be 256 or more")
+    split = _split.DEFAULT_SPLIT if split is None else int(split)
+    if split < 0:
+        raise ValueError("split must not be negative")
     data = bytes(data)
     ctx = ctx or default_context()
     n = len(data)
@@ -113,7 +167,7 @@ def decompress_gzip_file(data, ctx: Optional[Context] = None, chunk: Optional[in
         sub = cands[first:]
         m = len(sub)
         in_off, in_len, out_off, out_cap, total = layout(buf, n, sub, ctx)
-        out, out_len, status, _detail, in_used = _launch(buf, in_off, in_len, out_off, out_cap, total, ctx)
+        out, out_len, status, _detail, in_used = _launch(buf, in_off, in_len, out_off, out_cap, total, ctx, split, split_chunk)
         good = (status == _ffi.OK) & (out_len == out_cap) & (in_used == in_len)
         bad = np.flatnonzero(~good)
         j = int(bad[0]) if len(bad) else m

@@ -56,27 +56,29 @@ def _gf2_square(mat):
     return [_gf2_times(mat, mat[n]) for n in range(32)]
 
 
+def _crc_zero_operators():
+    """Entry k: the operator of 2^k zero BYTES (k < 64: every length a uint64 holds)."""
+    bit = [0xedb88320] + [1 << n for n in range(31)]  # one zero bit
+    ops = [_gf2_square(_gf2_square(_gf2_square(bit)))]
+    while len(ops) < 64:
+        ops.append(_gf2_square(ops[-1]))
+    return tuple(ops)
+
+
+_CRC_ZEROS = _crc_zero_operators()  # made once, at import, and never changed: a combine is one product per set bit of the length
+
+
 def crc32_combine(c1: int, c2: int, len2: int) -> int:
     """CRC-32 (RFC 1952) of A + B from crc32(A), crc32(B) and len(B): crc32(A) advanced over len(B) zero bytes -- the operator for
     one zero bit as a 32 x 32 matrix over GF(2), squared once per bit of the length -- plus crc32(B)."""
     if len2 <= 0:
         return c1
-    odd = [0xedb88320] + [1 << n for n in range(31)]  # one zero bit
-    even = _gf2_square(odd)   # two
-    odd = _gf2_square(even)   # four
-    while True:
-        even = _gf2_square(odd)  # (first round: one zero byte)
+    k = 0
+    while len2:
         if len2 & 1:
-            c1 = _gf2_times(even, c1)
+            c1 = _gf2_times(_CRC_ZEROS[k], c1)
         len2 >>= 1
-        if not len2:
-            break
-        odd = _gf2_square(even)
-        if len2 & 1:
-            c1 = _gf2_times(odd, c1)
-        len2 >>= 1
-        if not len2:
-            break
+        k += 1
     return c1 ^ c2
 
 
@@ -143,6 +145,31 @@ def _fingerprint(data, end: int) -> Tuple[int, int]:
 
 def _np(data) -> np.ndarray:
     return np.frombuffer(data, dtype=np.uint8) if len(data) else np.zeros(0, dtype=np.uint8)
+
+
+def segments_of(points, body_len: int, out_len: int):
+    """The segments the access points cut a body of body_len bytes and out_len decoded bytes into:
+    [(in_off, in_len, start_bit, end_bit, a, b)] -- input bytes of the BODY, the bit its first block starts at inside the first of
+    them, the bit its last block ends at counted from that byte (0: the final block), and the output range it produces."""
+    cuts = [(0, 0)] + [(int(b), int(p)) for b, p in points]
+    segs = []
+    for k, (bit, a) in enumerate(cuts):
+        off = bit >> 3
+        if k + 1 < len(cuts):
+            end = cuts[k + 1][0] - 8 * off
+            segs.append((off, (end + 7) >> 3, bit & 7, end, a, cuts[k + 1][1]))
+        else:
+            segs.append((off, body_len - off, bit & 7, 0, a, out_len))
+    return segs
+
+
+def window_extent(k: int, out_pos: int, first_row: int = 0):
+    """(offset, length) of the dictionary of segment k of a stream inside its windows (rows of 32768 bytes from row first_row on):
+    segment k > 0 starts at point k - 1, whose window is the last min(out_pos, 32768) bytes of that point's row; segment 0 has none."""
+    if k == 0 or out_pos == 0:
+        return 0, 0
+    w = min(out_pos, WINDOW)
+    return (first_row + k - 1) * WINDOW + (WINDOW - w), w
 
 
 class Index:
@@ -294,16 +321,7 @@ class Index:
     def segments(self):
         """[(in_off, in_len, start_bit, end_bit, a, b)]: input bytes of the BODY, the bit its first block starts at inside the first of
         them, the bit its last block ends at counted from that byte (0: the final block), and the output range it produces."""
-        cuts = [(0, 0)] + [(int(b), int(p)) for b, p in self.points]
-        segs = []
-        for k, (bit, a) in enumerate(cuts):
-            off = bit >> 3
-            if k + 1 < len(cuts):
-                end = cuts[k + 1][0] - 8 * off
-                segs.append((off, (end + 7) >> 3, bit & 7, end, a, cuts[k + 1][1]))
-            else:
-                segs.append((off, self.body_len - off, bit & 7, 0, a, self.out_len))
-        return segs
+        return segments_of(self.points, self.body_len, self.out_len)
 
     def _check_pair(self, data) -> Optional[DecompressionError]:
         if _fingerprint(data, self.body_off + self.body_len) != self.fingerprint:
@@ -324,11 +342,9 @@ class Index:
         end_bit = np.array([s[3] for s in segs], dtype=np.uint64)
         out_off = np.array([s[4] - base for s in segs], dtype=np.uint64)
         out_cap = np.array([s[5] - s[4] for s in segs], dtype=np.uint64)
-        # segment k > 0 of the stream starts at point k - 1: its window is the last min(out_pos, 32768) bytes of row k - 1
-        w = np.array([min(s[4], WINDOW) if first + j > 0 else 0 for j, s in enumerate(segs)], dtype=np.uint64)
-        rows = np.array([max(first + j - 1, 0) for j in range(m)], dtype=np.uint64)
-        dict_off = rows * np.uint64(WINDOW) + (np.uint64(WINDOW) - w)
-        dict_off[w == 0] = 0
+        ext = [window_extent(first + j, s[4]) for j, s in enumerate(segs)]
+        dict_off = np.array([e[0] for e in ext], dtype=np.uint64)
+        w = np.array([e[1] for e in ext], dtype=np.uint64)
         windows = self.windows if len(self.windows) else np.zeros((1, WINDOW), dtype=np.uint8)
         out = np.empty(total + 16, dtype=np.uint8)
         out_len = np.zeros(m, dtype=np.uint64)

@@ -255,6 +255,33 @@ class Context:
         _ffi.check(rc, self._h)
         return out_len, status, detail, in_used, adler
 
+    # -- the parallel index scan over many raw streams (host memory) -------------------------------
+    def index_scan_many(self, in_buf: np.ndarray, in_off, in_len, point_off, chunk: int = 0, span: int = 0, windows: bool = True):
+        """Thin wrapper of pzg_index_scan_many on a host numpy buffer: stream s is in_buf[in_off[s] : in_off[s] + in_len[s]] and owns
+        the slots point_off[s] .. point_off[s + 1] (point_off: n + 1 entries, ascending).  chunk 0: 128 KiB; span 0: 1 MiB.
+        Returns (points u64[slots,2], windows u8[slots,32768] or None, npoints u32[n], out_len u64[n], status i32[n], detail u32[n,2],
+        in_used u64[n]); raises PzgError (rc -4 when the device has not the memory the call needs)."""
+        in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
+        in_len = np.ascontiguousarray(in_len, dtype=np.uint64)
+        point_off = np.ascontiguousarray(point_off, dtype=np.uint32)
+        n = len(in_off)
+        if len(in_len) != n or len(point_off) != n + 1:
+            raise ValueError("in_off, in_len: n entries; point_off: n + 1")
+        slots = int(point_off[-1])
+        points = np.zeros((max(slots, 1), 2), dtype=np.uint64)
+        wins = np.zeros((max(slots, 1), 32768), dtype=np.uint8) if windows else None
+        npoints = np.zeros(n, dtype=np.uint32)
+        out_len = np.zeros(n, dtype=np.uint64)
+        status = np.full(n, -1, dtype=np.int32)
+        detail = np.zeros((n, 2), dtype=np.uint32)
+        in_used = np.zeros(n, dtype=np.uint64)
+        rc = self._L.pzg_index_scan_many(self._h, in_buf.ctypes.data, in_off.ctypes.data, in_len.ctypes.data, n, int(chunk), int(span),
+                                         points.ctypes.data, point_off.ctypes.data, npoints.ctypes.data,
+                                         wins.ctypes.data if windows else None, out_len.ctypes.data, status.ctypes.data, detail.ctypes.data,
+                                         in_used.ctypes.data, 0)
+        _ffi.check(rc, self._h)
+        return points[:slots], (wins[:slots] if windows else None), npoints, out_len, status, detail, in_used
+
     # -- device-pointer call (the timed path; pointers are raw integers) ----------------------------
     def decompress_many_device(self, in_base: int, in_off: int, in_len: int, out_base: int, out_off: int,
                                out_cap: int, out_len: int, status: int, detail: int, in_used: int, adler: int,
