@@ -90,6 +90,8 @@ extern "C" {
 #define PZG_E_DICT               20  /* "Header error: preset dictionary mismatch: <hex d0> != <hex d1>": the stream's DICTID (d0) is
                                       * not the Adler-32 of the dictionary supplied for it (d1) */
 #define PZG_E_SEGMENT 21  /* segments only: the blocks do not end at end_bit. d0 = 1 final block came first, 2 a block ran past; d1 = bit reached */
+#define PZG_E_FILTER 23  /* (0.5) pzg_unfilter_many only: row d0 has filter byte d1 (> 4).  d0 = 0xffffffff: the image's bpp (d1) or its
+                            stride is not legal -- device arrays only, the host-pointer form refuses the call */
 #define PZG_E_SCAN 22  /* pzg_index_scan only: the chain of blocks did not reach the final block.
                           d0 = the status the chain's last segment met (0: a dead wave),
                           d1 = low 32 bits of that segment's start bit.
@@ -464,6 +466,38 @@ PZG_API int pzg_gzip_layout(pzg_ctx *ctx, const uint8_t *in, uint64_t in_len,
         const uint64_t *starts, uint32_t m, uint64_t out_base_off,
         uint64_t *in_off, uint64_t *in_lenv, uint64_t *out_off,
         uint64_t *out_cap, uint64_t *total, uint32_t flags);
+
+/*
+ * pzg_unfilter_many (0.5): EXTENSION -- scanline unfiltering, the second half of a PNG decode (PNG specification section 9) and of a
+ * PDF FlateDecode stream with Predictor 10-15; a wavefront per image, all n in one launch.  Nothing in it knows of PNG:
+ *   image i     height[i] rows of 1 + row_bytes[i] bytes at src_base + src_off[i]: a filter byte (0 None, 1 Sub, 2 Up, 3 Average,
+ *               4 Paeth) and the filtered bytes.  bpp[i] is the filter unit in bytes: 1, 2, 3, 4, 6 or 8.
+ *   delivery    row r, without its filter byte, at dst_base + dst_off[i] + r * dst_stride[i] (dst_stride[i] >= row_bytes[i]).  The
+ *               bytes between row_bytes and the stride and everything outside the extents are untouched.  The dst extents overlap
+ *               neither each other nor src.
+ *   status[i]   PZG_OK
+ *               PZG_E_FILTER     row d0 has the filter byte d1 > 4: rows [0, d0) are delivered, nothing of row d0 onward is written
+ *               PZG_E_TRUNCATED  src_len[i] < height * (1 + row_bytes): d0 is the number of rows that lie wholly inside src_len;
+ *                                they are delivered -- unless one of them has a bad filter byte, which then wins.  The filter
+ *                                bytes of the rows that do not lie wholly inside are not looked at.
+ *               height or row_bytes of 0: PZG_OK, nothing read or written.
+ *   detail      2n words (d0, d1 per image), or NULL.
+ * flags: 0 -- every pointer is host memory: the call stages src, the arrays and dst's extents through the context's arenas and
+ * returns when dst and status are filled; PZG_DEVICE_PTRS -- every pointer is device memory, the launch goes on the context's
+ * stream (pzg_set_stream) in call order, and with PZG_ASYNC as well the call only enqueues: pzg_decompress_many(... PZG_ASYNC),
+ * pzg_unfilter_many(... PZG_ASYNC) and pzg_sync chain without a host round trip, and src_len may be the out_len array the decode
+ * wrote (that is why it is an argument).  pzg_last_kernel_ms reports the launch.
+ * PZG_RC_BAD_ARG: n == 0, any other flag, a null array, a context of several devices; with host pointers also a bpp outside
+ * {1, 2, 3, 4, 6, 8} and a stride below row_bytes (of an image that has rows).  Device arrays are not read by the host: there such
+ * an image gets PZG_E_FILTER with d0 = 0xffffffff (d1 = its bpp) and nothing of it is read or written.
+ * Offsets and strides are 64-bit.  Nothing is read but the aligned dwords that hold bytes of src_off[i] .. + src_len[i].
+ */
+PZG_API int pzg_unfilter_many(pzg_ctx *ctx,
+        const uint8_t *src_base, const uint64_t *src_off, const uint64_t *src_len,
+        uint8_t *dst_base, const uint64_t *dst_off, const uint64_t *dst_stride,
+        const uint32_t *row_bytes, const uint32_t *height, const uint8_t *bpp,
+        int32_t *status, uint32_t *detail,   /* detail: 2n, or NULL */
+        uint32_t n, uint32_t flags);         /* 0, PZG_DEVICE_PTRS, PZG_DEVICE_PTRS | PZG_ASYNC */
 
 /*
  * decompressIncremental / ZlibDecoder (Zlib.hs:3-8, Monad.hs:163-197; driver Deflate.hs:30-48), batched: a pzg_decoder

@@ -46,6 +46,7 @@
 #include "pzg_helpers.h"
 #include "pzg_launch.h"
 #include "scan_core.h"  // (ScanStream, ScanResult: the tables of pzg_index_scan_many)
+#include "pzg_unfilter_kernel.h"  // (unfilter_kernel and its launcher; unfilter_core.h: its statuses, and what it takes for a legal bpp)
 
 namespace {
 
@@ -1777,6 +1778,116 @@ int pzg_gzip_layout(pzg_ctx *ctx, const uint8_t *in, uint64_t in_len, const uint
         if (!dev) {
             uint64_t *const host[4] = {in_off, in_lenv, out_off, out_cap};
             for (int k = 0; k < 4; ++k) HIP_TRY(ctx, hipMemcpy(host[k], d + k * row, 8 * (size_t)m, hipMemcpyDeviceToHost));
+        }
+        return PZG_RC_OK;
+    });
+}
+
+// Scanline unfiltering (unfilter_core.h): the device-pointer form is one launch on the context's stream; the host-pointer form stages
+// the span of src that holds the images, the arrays and the span of dst that holds the extents through lane 0's arenas, and copies
+// the delivered rows -- nothing else -- from the staged span into the caller's dst.
+int pzg_unfilter_many(pzg_ctx *ctx, const uint8_t *src_base, const uint64_t *src_off, const uint64_t *src_len, uint8_t *dst_base, const uint64_t *dst_off,
+                      const uint64_t *dst_stride, const uint32_t *row_bytes, const uint32_t *height, const uint8_t *bpp, int32_t *status,
+                      uint32_t *detail, uint32_t n, uint32_t flags)
+{
+    static_assert(pzg::Unfilter::ST_FILTER == PZG_E_FILTER && pzg::Unfilter::ST_TRUNCATED == PZG_E_TRUNCATED && pzg::Unfilter::ST_OK == PZG_OK,
+                  "the core's statuses are the header's");
+    if (!ctx_live(ctx) || n == 0) return PZG_RC_BAD_ARG;
+    if ((flags & ~(PZG_DEVICE_PTRS | PZG_ASYNC)) || ((flags & PZG_ASYNC) && !(flags & PZG_DEVICE_PTRS))) return PZG_RC_BAD_ARG;
+    if (ctx->shards.size() != 1) return PZG_RC_BAD_ARG;
+    if (!src_base || !src_off || !src_len || !dst_base || !dst_off || !dst_stride || !row_bytes || !height || !bpp || !status) return PZG_RC_BAD_ARG;
+    Shard &sh = *ctx->shards[0];
+    if (flags & PZG_DEVICE_PTRS)
+        return guarded(ctx, "pzg_unfilter_many", [&]() -> int {
+            std::lock_guard<std::mutex> g(sh.mu);
+            HIP_TRY(ctx, hipSetDevice(sh.device));
+            pzg::UnfilterArgs a{src_base, src_off, src_len, dst_base, dst_off, dst_stride, row_bytes, height, bpp, status, detail, n};
+            HIP_TRY(ctx, hipEventRecord(sh.ev0, sh.stream));
+            HIP_TRY(ctx, pzg::launch_unfilter(a, sh.stream));
+            HIP_TRY(ctx, hipEventRecord(sh.ev1, sh.stream));
+            sh.timed = true;
+            sh.last_was_host = false;
+            if (!(flags & PZG_ASYNC)) HIP_TRY(ctx, hipStreamSynchronize(sh.stream));
+            return PZG_RC_OK;
+        });
+    // host pointers: the spans, and what the device form leaves to the kernel
+    uint64_t s_lo = ~0ull, s_hi = 0, d_lo = ~0ull, d_hi = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (row_bytes[i] == 0u || height[i] == 0u) continue;
+        if (!pzg::Unfilter::bpp_ok(bpp[i]) || dst_stride[i] < row_bytes[i]) return PZG_RC_BAD_ARG;
+        const uint64_t d_end = dst_off[i] + (uint64_t)(height[i] - 1u) * dst_stride[i] + row_bytes[i];
+        d_lo = std::min(d_lo, dst_off[i]);
+        d_hi = std::max(d_hi, d_end);
+        if (src_len[i] == 0u) continue;
+        s_lo = std::min(s_lo, src_off[i]);
+        s_hi = std::max(s_hi, src_off[i] + src_len[i]);
+    }
+    if (d_lo > d_hi) {  // nothing but empty images
+        for (uint32_t i = 0; i < n; ++i) status[i] = PZG_OK;
+        if (detail) memset(detail, 0, 8 * (size_t)n);
+        return PZG_RC_OK;
+    }
+    if (s_lo > s_hi) s_lo = s_hi = 0;
+    return guarded(ctx, "pzg_unfilter_many", [&]() -> int {
+        LaneCall call(ctx, sh);
+        if (call.rc != PZG_RC_OK) return call.rc;
+        Lane &ln = call.ln;
+        hipStream_t st = call.st;
+        int rc;
+        // the spans keep their places modulo 16: a row is fetched and stored at the alignment the caller gave it
+        const size_t s_skew = (size_t)((uintptr_t)(src_base + s_lo) & 15u), d_skew = (size_t)((uintptr_t)(dst_base + d_lo) & 15u);
+        const size_t s_bytes = (size_t)(s_hi - s_lo), d_bytes = (size_t)(d_hi - d_lo);
+        const size_t row8 = pad256(8 * (size_t)n), row4 = pad256(4 * (size_t)n);
+        const size_t m_in = 4 * row8 + 2 * row4 + pad256(n), m_all = m_in + row4 + pad256(8 * (size_t)n);
+        if ((rc = arena_reserve(ctx, ln.d_in[0], s_bytes + 64)) != PZG_RC_OK) return rc;
+        if ((rc = arena_reserve(ctx, ln.d_out[0], d_bytes + 64)) != PZG_RC_OK) return rc;
+        if ((rc = arena_reserve(ctx, ln.d_meta[0], m_all)) != PZG_RC_OK) return rc;
+        if ((rc = pinned_reserve(ctx, ln.h_meta[0], m_all)) != PZG_RC_OK) return rc;
+        if ((rc = pinned_reserve(ctx, ln.h_out[0], d_bytes + 64)) != PZG_RC_OK) return rc;
+        uint8_t *hm = ln.h_meta[0].p, *dm = (uint8_t *)ln.d_meta[0].p;
+        uint64_t *h_soff = (uint64_t *)(void *)hm, *h_slen = (uint64_t *)(void *)(hm + row8), *h_doff = (uint64_t *)(void *)(hm + 2 * row8);
+        for (uint32_t i = 0; i < n; ++i) {
+            const bool empty = row_bytes[i] == 0u || height[i] == 0u;
+            h_soff[i] = empty || src_len[i] == 0u ? 0u : src_off[i] - s_lo;
+            h_slen[i] = src_len[i];
+            h_doff[i] = empty ? 0u : dst_off[i] - d_lo;
+        }
+        memcpy(hm + 3 * row8, dst_stride, 8 * (size_t)n);
+        memcpy(hm + 4 * row8, row_bytes, 4 * (size_t)n);
+        memcpy(hm + 4 * row8 + row4, height, 4 * (size_t)n);
+        memcpy(hm + 4 * row8 + 2 * row4, bpp, n);
+        HIP_TRY(ctx, hipMemcpyAsync(dm, hm, m_in, hipMemcpyHostToDevice, st));
+        if (s_bytes) HIP_TRY(ctx, hipMemcpyAsync((uint8_t *)ln.d_in[0].p + s_skew, src_base + s_lo, s_bytes, hipMemcpyHostToDevice, st));
+        pzg::UnfilterArgs a{};
+        a.src_base = (const uint8_t *)ln.d_in[0].p + s_skew;
+        a.src_off = (const uint64_t *)(void *)dm;
+        a.src_len = (const uint64_t *)(void *)(dm + row8);
+        a.dst_base = (uint8_t *)ln.d_out[0].p + d_skew;
+        a.dst_off = (const uint64_t *)(void *)(dm + 2 * row8);
+        a.dst_stride = (const uint64_t *)(void *)(dm + 3 * row8);
+        a.row_bytes = (const uint32_t *)(void *)(dm + 4 * row8);
+        a.height = (const uint32_t *)(void *)(dm + 4 * row8 + row4);
+        a.bpp = dm + 4 * row8 + 2 * row4;
+        a.status = (int32_t *)(void *)(dm + m_in);
+        a.detail = (uint32_t *)(void *)(dm + m_in + row4);
+        a.n = n;
+        HIP_TRY(ctx, call.begin_timed());
+        HIP_TRY(ctx, pzg::launch_unfilter(a, st));
+        HIP_TRY(ctx, call.end_timed());
+        HIP_TRY(ctx, hipMemcpyAsync(hm + m_in, dm + m_in, m_all - m_in, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipMemcpyAsync(ln.h_out[0].p, a.dst_base, d_bytes, hipMemcpyDeviceToHost, st));
+        if ((rc = call.finish()) != PZG_RC_OK) return rc;
+        const int32_t *h_status = (const int32_t *)(const void *)(hm + m_in);
+        const uint32_t *h_detail = (const uint32_t *)(const void *)(hm + m_in + row4);
+        memcpy(status, h_status, 4 * (size_t)n);
+        if (detail) memcpy(detail, h_detail, 8 * (size_t)n);
+        for (uint32_t i = 0; i < n; ++i) {  // the rows the kernel delivered
+            if (row_bytes[i] == 0u || height[i] == 0u) continue;
+            const uint32_t rows = h_status[i] == PZG_OK ? height[i] : std::min(h_detail[2 * (size_t)i], height[i]);
+            for (uint32_t r = 0; r < rows; ++r) {
+                const uint64_t at = dst_off[i] + (uint64_t)r * dst_stride[i];
+                memcpy(dst_base + at, ln.h_out[0].p + (at - d_lo), row_bytes[i]);
+            }
         }
         return PZG_RC_OK;
     });

@@ -197,6 +197,10 @@ extern "C" int pzg_error_message(const uint8_t *in, uint64_t in_len, int32_t sta
     case PZG_E_DICT: snprintf(buf, buf_len, "Header error: preset dictionary mismatch: %x != %x", d0, d1); break;  // extension
     case PZG_E_SEGMENT: snprintf(buf, buf_len, "Format error: segment does not end on its block boundary"); break;  // extension
     case PZG_E_SCAN: snprintf(buf, buf_len, "Format error: the chain of blocks did not reach the final block"); break;  // extension
+    case PZG_E_FILTER:  // extension (pzg_unfilter_many)
+        if (d0 == 0xffffffffu) snprintf(buf, buf_len, "Block format error: filter unit of %u bytes, or a stride below the row", d1);
+        else snprintf(buf, buf_len, "Block format error: row %u has filter type %u", d0, d1);
+        break;
     default: snprintf(buf, buf_len, "unknown status %d", status); break;
     }
     return (int)strlen(buf);

@@ -181,6 +181,19 @@ size_t members_layout_scratch_bytes(uint64_t m);
 hipError_t launch_members_layout(const LayoutArgs &a, uint8_t *scratch, hipStream_t stream);
 const uint64_t *members_layout_total(uint64_t m, const uint8_t *scratch);
 
+// scanline unfiltering (pzg_unfilter_kernel.h, unfilter_core.h; compiled with pzg_api.cpp): a wave per image.  Every pointer is device memory.
+struct UnfilterArgs {
+    const uint8_t *src_base;
+    const uint64_t *src_off, *src_len;  // n
+    uint8_t *dst_base;
+    const uint64_t *dst_off, *dst_stride;  // n
+    const uint32_t *row_bytes, *height;    // n
+    const uint8_t *bpp;                    // n
+    int32_t *status;                       // n
+    uint32_t *detail;                      // 2n or null
+    uint32_t n;
+};
+
 // partials: 3 * 4 * ceil(max_waves / 4) uint32 of device scratch
 hipError_t launch_adler32(const uint8_t *buf, uint64_t len, uint32_t init, uint32_t *partials, uint32_t max_waves,
                           uint32_t *out, hipStream_t stream);

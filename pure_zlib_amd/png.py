@@ -1,0 +1,257 @@
+"""PNG images decoded in batches on the GPU: EXTENSION, the reference has no image reader.
+
+A PNG's IDAT chunks are ONE RFC 1950 stream and IHDR gives its exact decoded size, height * (1 + row_bytes), so a batch of images
+is one pzg_decompress_many launch with exact capacities -- no capacity guess, no relaunch -- and one pzg_unfilter_many launch behind
+it on the same stream, which takes the decode's out_len array as its src_len: the scanline filters (PNG specification section 9)
+are undone on the device, a wavefront per image, and only the pixels come back, in one copy.  The host parses the chunks and
+checks their CRC-32s with the system's zlib; nothing is inflated on the CPU.  Device memory is held in torch tensors.
+
+    read_png_many(blobs_or_paths)  -> [PngImage, or the DecompressionError / ValueError / NotImplementedError of that image]
+    read_png(blob_or_path)         -> PngImage                  (raises)
+    test_png_many(blobs_or_paths)  -> [(index_or_name, problem)]   (empty: every image is sound)
+    python -m pure_zlib_amd.png -t A.png B.png ...
+
+Colour types 0, 2, 3, 4 and 6 at their legal bit depths, not interlaced (an Adam7 image is NotImplementedError, for that image
+only).  `data` is the samples as the file stores them -- no palette expansion, no gamma, no alpha handling: a viewer's work.
+"""
+import os
+import struct
+import sys
+import zlib as _sys_zlib  # crc32 of the chunks only
+from dataclasses import dataclass
+from typing import List, Optional, Sequence, Tuple, Union
+
+import numpy as np
+
+from . import _ffi
+from .zlib import Context, DecompressionError, PinnedArena, default_context, error_from_status
+
+SIGNATURE = b"\x89PNG\r\n\x1a\n"
+_CHANNELS = {0: 1, 2: 3, 3: 1, 4: 2, 6: 4}
+_DEPTHS = {0: (1, 2, 4, 8, 16), 2: (8, 16), 3: (1, 2, 4, 8), 4: (8, 16), 6: (8, 16)}
+
+
+@dataclass
+class PngImage:
+    width: int
+    height: int
+    color_type: int
+    bit_depth: int
+    palette: Optional[bytes]  # PLTE as it stands (3 bytes an entry), or None
+    trns: Optional[bytes]     # tRNS as it stands, or None
+    data: Optional[np.ndarray]  # (H, W, C) uint8 | (H, W, C) >u2 | (H, row_bytes) packed uint8 below 8 bits; None with device_out
+
+    @property
+    def channels(self) -> int:
+        return _CHANNELS[self.color_type]
+
+    @property
+    def row_bytes(self) -> int:
+        return (self.width * self.channels * self.bit_depth + 7) // 8
+
+    @property
+    def bpp(self) -> int:
+        return max(1, self.channels * self.bit_depth // 8)
+
+
+def _format_error(msg: str) -> DecompressionError:
+    return DecompressionError("FormatError", msg, _ffi.E_FILTER)
+
+
+def _parse(name: str, blob: bytes) -> Tuple[PngImage, bytes]:
+    """(the image without its data, its IDAT payloads joined); raises ValueError / NotImplementedError naming the image."""
+    if blob[:8] != SIGNATURE:
+        raise ValueError("%s: not a PNG file (bad signature)" % name)
+    at, img, idat, seen_idat, idat_closed, palette, trns = 8, None, [], False, False, None, None
+    while True:
+        if at + 12 > len(blob):
+            raise ValueError("%s: file ends inside a chunk (no IEND)" % name)
+        length, kind = struct.unpack_from(">I4s", blob, at)
+        if at + 12 + length > len(blob):
+            raise ValueError("%s: chunk %s runs past the end of the file" % (name, kind.decode("latin-1")))
+        body = blob[at + 8:at + 8 + length]
+        crc, = struct.unpack_from(">I", blob, at + 8 + length)
+        have = _sys_zlib.crc32(body, _sys_zlib.crc32(kind))
+        if crc != have:
+            raise ValueError("%s: chunk %s: checksum mismatch: %08x != %08x" % (name, kind.decode("latin-1"), crc, have))
+        at += 12 + length
+        if img is None and kind != b"IHDR":
+            raise ValueError("%s: the first chunk is %s, not IHDR" % (name, kind.decode("latin-1")))
+        if kind == b"IHDR":
+            if img is not None or length != 13:
+                raise ValueError("%s: bad IHDR" % name)
+            w, h, depth, ctype, comp, filt, lace = struct.unpack(">IIBBBBB", body)
+            if ctype not in _DEPTHS or depth not in _DEPTHS[ctype]:
+                raise ValueError("%s: colour type %d with bit depth %d is not a PNG image type" % (name, ctype, depth))
+            if w == 0 or h == 0 or w >> 31 or h >> 31 or comp != 0 or filt != 0 or lace > 1:
+                raise ValueError("%s: bad IHDR (size %d x %d, compression %d, filter %d, interlace %d)" % (name, w, h, comp, filt, lace))
+            if lace == 1:
+                raise NotImplementedError("%s: Adam7-interlaced images are not supported" % name)
+            img = PngImage(w, h, ctype, depth, None, None, None)
+            if img.row_bytes >> 32:
+                raise ValueError("%s: a row of %d bytes" % (name, img.row_bytes))
+        elif kind == b"IDAT":
+            if idat_closed:
+                raise ValueError("%s: IDAT chunks are not consecutive" % name)
+            seen_idat = True
+            idat.append(body)
+        elif kind == b"IEND":
+            break
+        else:
+            idat_closed = seen_idat
+            if kind == b"PLTE":
+                if length % 3 or length == 0 or length > 768 or seen_idat:
+                    raise ValueError("%s: bad PLTE" % name)
+                palette = body
+            elif kind == b"tRNS":
+                trns = body
+            elif not kind[0] & 0x20:
+                raise ValueError("%s: unknown critical chunk %s" % (name, kind.decode("latin-1")))
+    if not seen_idat:
+        raise ValueError("%s: no IDAT chunk" % name)
+    if img.color_type == 3 and palette is None:
+        raise ValueError("%s: a palette image without PLTE" % name)
+    img.palette, img.trns = palette, trns
+    return img, b"".join(idat)
+
+
+def _shape(img: PngImage, flat: np.ndarray) -> np.ndarray:
+    if img.bit_depth == 8:
+        return flat.reshape(img.height, img.width, img.channels)
+    if img.bit_depth == 16:
+        return flat.view(">u2").reshape(img.height, img.width, img.channels)
+    return flat.reshape(img.height, img.row_bytes)
+
+
+def _load(src) -> Tuple[Optional[str], bytes]:
+    if isinstance(src, (bytes, bytearray, memoryview)):
+        return None, bytes(src)
+    with open(src, "rb") as f:
+        return os.fspath(src), f.read()
+
+
+def read_png_many(blobs_or_paths: Sequence[Union[str, os.PathLike, bytes, bytearray, memoryview]], ctx: Optional[Context] = None,
+                  device_out: Optional[Tuple[int, Sequence[int], Sequence[int]]] = None) -> List[Union[PngImage, Exception]]:
+    """Every image of the batch, or in its place the exception that read_png would raise for it: a bad image never disturbs its
+    neighbours.  device_out = (ptr, offsets, strides): the rows of image i land at ptr + offsets[i] + r * strides[i] in device
+    memory of the caller's (a torch tensor's data_ptr()), nothing is copied out and `data` is None."""
+    import torch
+    results: List[Union[PngImage, Exception, None]] = [None] * len(blobs_or_paths)
+    names, good = [], []  # good: (index, image, stream)
+    for k, src in enumerate(blobs_or_paths):
+        name = "#%d" % k
+        try:
+            path, blob = _load(src)
+            name = path or name
+            img, z = _parse(name, blob)
+            good.append((k, img, z))
+        except (ValueError, NotImplementedError, OSError) as e:
+            results[k] = e
+        names.append(name)
+    if not good:
+        return results
+    n = len(good)
+    pad = lambda a: (a + np.uint64(15)) & ~np.uint64(15)  # noqa: E731  (16-byte aligned extents: the wide store path)
+    in_len = np.array([len(z) for _k, _i, z in good], dtype=np.uint64)
+    row_bytes = np.array([i.row_bytes for _k, i, _z in good], dtype=np.uint32)
+    height = np.array([i.height for _k, i, _z in good], dtype=np.uint32)
+    bpp = np.array([i.bpp for _k, i, _z in good], dtype=np.uint8)
+    dec_cap = height.astype(np.uint64) * (row_bytes.astype(np.uint64) + np.uint64(1))
+    pix = height.astype(np.uint64) * row_bytes.astype(np.uint64)
+    in_off, dec_off, pix_off = (np.zeros(n, dtype=np.uint64) for _ in range(3))
+    in_off[1:] = np.cumsum(pad(in_len))[:-1]
+    dec_off[1:] = np.cumsum(pad(dec_cap + np.uint64(4)))[:-1]  # (4: a stream that decodes to MORE than its capacity claims no neighbour's dword)
+    pix_off[1:] = np.cumsum(pad(pix))[:-1]
+    stride = row_bytes.astype(np.uint64)
+    if device_out is not None:
+        out_ptr = int(device_out[0])
+        pix_off = np.array([device_out[1][k] for k, _i, _z in good], dtype=np.uint64)
+        stride = np.array([device_out[2][k] for k, _i, _z in good], dtype=np.uint64)
+        if (stride < row_bytes).any():
+            raise ValueError("device_out: a stride below the image's row_bytes")
+    tot_in = int(in_off[-1] + pad(in_len)[-1]) + 16
+    tot_dec = int(dec_off[-1] + pad(dec_cap + np.uint64(4))[-1]) + 16
+    tot_pix = int(pix_off[-1] + pad(pix)[-1]) + 16
+    ctx = ctx or default_context()
+    dev = torch.device("cuda", ctx.device)
+    ain = PinnedArena(tot_in)
+    try:
+        for j, (_k, _i, z) in enumerate(good):
+            ain.a[int(in_off[j]):int(in_off[j]) + len(z)] = np.frombuffer(z, dtype=np.uint8)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8)).to(dev)  # noqa: E731
+        d_in = up(ain.a[:tot_in])
+        d_meta = [up(a) for a in (in_off, in_len, dec_off, dec_cap, pix_off, stride, row_bytes, height, bpp)]
+        d_dec = torch.empty(tot_dec, dtype=torch.uint8, device=dev)
+        d_pix = torch.empty(tot_pix, dtype=torch.uint8, device=dev) if device_out is None else None
+        d_out_len = torch.zeros(8 * n, dtype=torch.uint8, device=dev)
+        d_status = torch.zeros(2 * 4 * n, dtype=torch.uint8, device=dev)   # the decode's, the unfilter's
+        d_detail = torch.zeros(2 * 8 * n, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)
+        p = [t.data_ptr() for t in d_meta]
+        ctx.decompress_many_device(d_in.data_ptr(), p[0], p[1], d_dec.data_ptr(), p[2], p[3], d_out_len.data_ptr(), d_status.data_ptr(),
+                                   d_detail.data_ptr(), 0, 0, n, sync=False)
+        ctx.unfilter_many_device(d_dec.data_ptr(), p[2], d_out_len.data_ptr(), out_ptr if device_out is not None else d_pix.data_ptr(), p[4], p[5],
+                                 p[6], p[7], p[8], d_status.data_ptr() + 4 * n, d_detail.data_ptr() + 8 * n, n, sync=False)
+        ctx.sync()
+        out_len = d_out_len.cpu().numpy().view(np.uint64)
+        status = d_status.cpu().numpy().view(np.int32).reshape(2, n)
+        detail = d_detail.cpu().numpy().view(np.uint32).reshape(2, n, 2)
+        pixels = d_pix.cpu().numpy() if d_pix is not None else None  # the one copy out
+    finally:
+        ain.close()
+    for j, (k, img, z) in enumerate(good):
+        name, st, ust = names[k], int(status[0, j]), int(status[1, j])
+        if st == _ffi.E_OUT_TOO_SMALL:
+            results[k] = _format_error("%s: too much image data" % name)
+        elif st != _ffi.OK:
+            e = error_from_status(z, st, detail[0, j])
+            results[k] = DecompressionError(e.constructor, "%s: %s" % (name, e.message), e.status, e.detail)
+        elif int(out_len[j]) != int(dec_cap[j]):
+            results[k] = _format_error("%s: not enough image data" % name)
+        elif ust == _ffi.E_FILTER:
+            results[k] = DecompressionError("FormatError", "%s: row %d has filter type %d" % (name, int(detail[1, j, 0]), int(detail[1, j, 1])),
+                                            ust, (int(detail[1, j, 0]), int(detail[1, j, 1])))
+        elif ust != _ffi.OK:
+            results[k] = _format_error("%s: not enough image data" % name)
+        else:
+            if pixels is not None:
+                o = int(pix_off[j])
+                img.data = _shape(img, pixels[o:o + int(pix[j])].copy())
+            results[k] = img
+    return results
+
+
+def read_png(blob_or_path, ctx: Optional[Context] = None) -> PngImage:
+    """One image.  Raises what read_png_many would put in its place."""
+    r = read_png_many([blob_or_path], ctx)[0]
+    if isinstance(r, Exception):
+        raise r
+    return r
+
+
+def test_png_many(blobs_or_paths, ctx: Optional[Context] = None) -> List[Tuple[Union[int, str], str]]:
+    """What `pngcheck` does for a batch: [(index or path, problem)] for every image read_png would refuse."""
+    out = []
+    for k, (src, r) in enumerate(zip(blobs_or_paths, read_png_many(blobs_or_paths, ctx))):
+        if isinstance(r, Exception):
+            out.append((k if isinstance(src, (bytes, bytearray, memoryview)) else os.fspath(src), str(r)))
+    return out
+
+
+test_png_many.__test__ = False  # (not a pytest test, whatever imports it)
+
+
+def main(argv=None) -> int:
+    argv = sys.argv[1:] if argv is None else list(argv)
+    if len(argv) >= 2 and argv[0] == "-t":
+        bad = test_png_many(argv[1:])
+        for name, why in bad:
+            print("%s: %s" % (name, why))
+        print("%d image(s): %s" % (len(argv) - 1, "%d bad" % len(bad) if bad else "OK"))
+        return 1 if bad else 0
+    print("usage: python -m pure_zlib_amd.png -t A.png B.png ...", file=sys.stderr)
+    return 2
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -116,6 +116,7 @@ _STATUS_CONSTRUCTOR = {
     _ffi.E_GZIP_HEADER: "HeaderError",   # extension (PZG_GZIP): the reference has no gzip
     _ffi.E_GZIP_ISIZE: "ChecksumError",
     _ffi.E_DICT: "HeaderError",         # extension (preset dictionaries)
+    _ffi.E_FILTER: "FormatError",       # extension (pzg_unfilter_many)
 }
 
 
@@ -291,6 +292,31 @@ class Context:
         rc = self._L.pzg_decompress_many(self._h, in_base, in_off, in_len, out_base, out_off, out_cap, out_len,
                                          status, detail or None, in_used or None, adler or None, n, flags)
         _ffi.check(rc, self._h)
+
+    # -- scanline unfiltering (pzg_unfilter_many) -----------------------------------------------------
+    def unfilter_many(self, src: np.ndarray, src_off, src_len, dst: np.ndarray, dst_off, dst_stride, row_bytes, height, bpp):
+        """Thin wrapper of pzg_unfilter_many on host numpy buffers: image i is height[i] rows of a filter byte and row_bytes[i]
+        filtered bytes at src[src_off[i]:], delivered without the filter bytes at dst[dst_off[i] + r * dst_stride[i]:].
+        Returns (status i32[n], detail u32[n,2])."""
+        arrs = [np.ascontiguousarray(a, dtype=t) for a, t in ((src_off, np.uint64), (src_len, np.uint64), (dst_off, np.uint64),
+                                                              (dst_stride, np.uint64), (row_bytes, np.uint32), (height, np.uint32), (bpp, np.uint8))]
+        n = len(arrs[0])
+        status = np.full(n, -1, dtype=np.int32)
+        detail = np.zeros((n, 2), dtype=np.uint32)
+        rc = self._L.pzg_unfilter_many(self._h, src.ctypes.data, arrs[0].ctypes.data, arrs[1].ctypes.data, dst.ctypes.data, arrs[2].ctypes.data,
+                                       arrs[3].ctypes.data, arrs[4].ctypes.data, arrs[5].ctypes.data, arrs[6].ctypes.data, status.ctypes.data,
+                                       detail.ctypes.data, n, 0)
+        _ffi.check(rc, self._h)
+        return status, detail
+
+    def unfilter_many_device(self, src_base: int, src_off: int, src_len: int, dst_base: int, dst_off: int, dst_stride: int, row_bytes: int,
+                             height: int, bpp: int, status: int, detail: int, n: int, sync: bool = True):
+        """pzg_unfilter_many on device memory, every pointer an integer address as decompress_many_device takes them: the launch goes
+        on the context's stream behind what was enqueued before it, so src_len may be the out_len array of a decode enqueued with
+        sync=False, and dst_base memory of the caller's own (a torch tensor's data_ptr())."""
+        flags = _ffi.DEVICE_PTRS | (0 if sync else _ffi.ASYNC)
+        _ffi.check(self._L.pzg_unfilter_many(self._h, src_base, src_off, src_len, dst_base, dst_off, dst_stride, row_bytes, height, bpp,
+                                             status, detail or None, n, flags), self._h)
 
     def decompress_many_sharded(self, batches, sync: bool = True, gzip: bool = False, lpt: bool = False, raw: bool = False,
                                 crc32: bool = False):
