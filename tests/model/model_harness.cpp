@@ -8,6 +8,7 @@
 
 #include "../../pure_zlib_amd/csrc/inflate_core.h"
 #include "../../pure_zlib_amd/csrc/bundle_core.h"
+#include "model_input.h"
 
 struct pzm_result {
     int32_t status;
@@ -26,30 +27,11 @@ static uint32_t crc32_bits(const uint8_t *p, uint64_t n)
     return ~reg;
 }
 
-// The stream's input buffer.  By default padded on both sides with 8 bytes of 0xEE (the bit reader loads whole aligned dwords);
-// PZM_TIGHT_INPUT=1 in the environment: the allocation is exactly the aligned dwords that cover the stream, which ends at its end
-// (the stream starts `mis` = -len mod 4 bytes into it), so that under AddressSanitizer a read past those dwords is caught.
-struct InBuf {
-    uint8_t *buf;
-    const uint8_t *stream;
-};
-static InBuf in_buf(const uint8_t *in, uint64_t in_len, uint32_t front)
-{
-    InBuf b;
-    if (getenv("PZM_TIGHT_INPUT")) {
-        const uint64_t mis = (4u - (in_len & 3u)) & 3u;
-        b.buf = (uint8_t *)malloc(mis + in_len ? mis + in_len : 1);
-        memset(b.buf, 0xEE, mis);
-        if (in_len) memcpy(b.buf + mis, in, in_len);
-        b.stream = b.buf + mis;
-    } else {
-        b.buf = (uint8_t *)malloc(in_len + 16 + front);
-        memset(b.buf, 0xEE, in_len + 16 + front);
-        if (in_len) memcpy(b.buf + 8 + front, in, in_len);
-        b.stream = b.buf + 8 + front;
-    }
-    return b;
-}
+// The stream's input buffer: model_input.h.  Padded on both sides by default; PZM_TIGHT_INPUT in the environment: the allocation is
+// exactly the aligned dwords that cover the stream, so that under AddressSanitizer a read outside those dwords is caught
+// (tests/test_sanitizers.py and, for the gzip and FDICT instances, tests/test_sanitized_cores.py).
+typedef ModelInput InBuf;
+static InBuf in_buf(const uint8_t *in, uint64_t in_len, uint32_t front) { return model_input(in, in_len, front); }
 
 // the scratch a model "wave" keeps from one stream to the next (its profile is in it: strip_profile_learn)
 template <int RB, bool GZ>
@@ -117,16 +99,14 @@ static int resume_feed(uint8_t *state, const uint8_t *in, uint64_t in_len, uint3
 {
     auto *lds = (pzg::WaveLds<RB> *)aligned_alloc(16, (sizeof(pzg::WaveLds<RB>) + 15u) & ~(size_t)15u);
     memset(lds, 0xA5, sizeof(*lds));
-    uint8_t *buf = (uint8_t *)malloc(in_len + 16);
-    memset(buf, 0xEE, in_len + 16);
-    if (in_len) memcpy(buf + 8, in, in_len);
+    const InBuf ib = in_buf(in, in_len, 0);
     pzg::Decoder<RB, false, true> dec(*lds);
     pzg::StreamResult sr;
     // the wave's scratch (strips), as in run_one(); PZM_NO_STRIPS=1: the windows alone
     uint32_t *strip = getenv("PZM_NO_STRIPS") ? nullptr : (uint32_t *)malloc(sizeof(uint32_t) * pzg::Decoder<RB, false, true>::STRIP_WORDS);
     if (strip) memset(strip, 0xC3, sizeof(uint32_t) * pzg::Decoder<RB, false, true>::STRIP_WORDS);
     dec.strip = strip;
-    dec.run_resume((pzg::ResumeState *)state, (uint32_t *)(state + pzg::ResumeSlot<RB>::IMAGE_OFF), state + pzg::ResumeSlot<RB>::HIST_OFF, buf + 8,
+    dec.run_resume((pzg::ResumeState *)state, (uint32_t *)(state + pzg::ResumeSlot<RB>::IMAGE_OFF), state + pzg::ResumeSlot<RB>::HIST_OFF, ib.stream,
                    in_len, out, cap, final_input, &sr, chunks);
     r->status = sr.status;
     r->detail0 = sr.detail0;
@@ -135,7 +115,7 @@ static int resume_feed(uint8_t *state, const uint8_t *in, uint64_t in_len, uint3
     r->out_len = sr.out_len;
     r->in_used = sr.in_used;
     free(strip);
-    free(buf);
+    free(ib.buf);
     free(lds);
     return 0;
 }
@@ -191,19 +171,17 @@ int pzm_decompress_dict(const uint8_t *in, uint64_t in_len, const uint8_t *dict,
 {
     auto *lds = (pzg::WaveLds<15> *)aligned_alloc(16, sizeof(pzg::WaveLds<15>));
     memset(lds, 0xA5, sizeof(*lds));
-    uint8_t *buf = (uint8_t *)malloc(in_len + 16);
-    memset(buf, 0xEE, in_len + 16);
-    if (in_len) memcpy(buf + 8, in, in_len);
+    const InBuf ib = in_buf(in, in_len, 0);
     pzg::Decoder<15, false> dec(*lds);
     pzg::StreamResult sr;
-    dec.run(buf + 8, in_len, out, cap, &sr, dict, dict_len);
+    dec.run(ib.stream, in_len, out, cap, &sr, dict, dict_len);
     r->status = sr.status;
     r->detail0 = sr.detail0;
     r->detail1 = sr.detail1;
     r->adler = sr.adler;
     r->out_len = sr.out_len;
     r->in_used = sr.in_used;
-    free(buf);
+    free(ib.buf);
     free(lds);
     return 0;
 }

@@ -3,7 +3,10 @@
 // suite can check them against a plain-Python finder without a GPU.  Every buffer the core is handed has 64 guard bytes on both
 // sides -- the input none at all beyond the aligned dwords that hold it -- and a guard that changed is the call's return value.
 // Never linked into libpzg.so; the product has no CPU path.
-// With -DPZM_MAIN it is a program of its own (for a sanitizer build): model_members FILE... at three chunk sizes.
+// Built with AddressSanitizer (tests/test_sanitized_cores.py builds it so with tests/cxx/san_members.cpp and runs the files of
+// tests/memberscheck.py) every such buffer is instead a heap block of exactly its bytes: the sanitizer is the guard then, for reads
+// as well as writes.
+// With -DPZM_MAIN it is a program of its own: model_members FILE... at three chunk sizes.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -17,6 +20,22 @@ namespace {
 
 constexpr size_t GUARD = 64;
 
+#if defined(__SANITIZE_ADDRESS__)
+struct Guarded {
+    uint8_t *base = nullptr, *at = nullptr;
+    size_t n = 0;
+    explicit Guarded(size_t bytes) : n(bytes)
+    {
+        base = (uint8_t *)malloc(n ? n : 16);  // (no bytes: the address behind a block, where nothing may be touched)
+        memset(base, 0xA5, n ? n : 16);
+        at = n ? base : base + 16;
+    }
+    Guarded(const Guarded &) = delete;
+    ~Guarded() { free(base); }
+    uint8_t *p() const { return at; }
+    bool ok() const { return true; }
+};
+#else
 struct Guarded {
     uint8_t *base = nullptr;
     size_t n = 0;
@@ -37,6 +56,7 @@ struct Guarded {
         return true;
     }
 };
+#endif
 
 // The input at `mis` bytes past a dword boundary, as a device pointer may be, in a heap block of exactly the aligned dwords that
 // hold it: a sanitizer build sees any read outside them.

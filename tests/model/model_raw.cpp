@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include "../../pure_zlib_amd/csrc/inflate_core.h"
+#include "model_input.h"
 
 struct pzm_result {
     int32_t status;
@@ -22,28 +23,16 @@ static uint32_t *&kept_scratch()
 }
 
 // One stream.  The input is padded on both sides with 8 bytes of 0xEE (the bit reader loads whole aligned dwords), or with
-// PZM_TIGHT_INPUT=1 in the environment allocated as exactly the aligned dwords that cover it; PZM_NO_STRIPS=1: no scratch, the
-// windows alone.
+// PZM_TIGHT_INPUT in the environment allocated as exactly the aligned dwords that cover it (model_input.h; under ASan + UBSan in
+// tests/test_sanitized_cores.py, which hands over a dictionary of exactly dict_len bytes and an output of exactly cap);
+// PZM_NO_STRIPS=1: no scratch, the windows alone.
 template <int RB>
 static void run_one(const uint8_t *in, uint64_t in_len, const uint8_t *dict, uint32_t dict_len, uint8_t *out, uint64_t cap, pzm_result *r)
 {
     typedef pzg::Decoder<RB, false, false, true> RawDecoder;
     auto *lds = (pzg::WaveLds<RB> *)aligned_alloc(16, (sizeof(pzg::WaveLds<RB>) + 15u) & ~(size_t)15u);
     memset(lds, 0xA5, sizeof(*lds));  // LDS is not zero-initialised on the device either
-    uint8_t *buf;
-    const uint8_t *stream;
-    if (getenv("PZM_TIGHT_INPUT")) {
-        const uint64_t mis = (4u - (in_len & 3u)) & 3u;
-        buf = (uint8_t *)malloc(mis + in_len ? mis + in_len : 1);
-        memset(buf, 0xEE, mis);
-        if (in_len) memcpy(buf + mis, in, in_len);
-        stream = buf + mis;
-    } else {
-        buf = (uint8_t *)malloc(in_len + 16);
-        memset(buf, 0xEE, in_len + 16);
-        if (in_len) memcpy(buf + 8, in, in_len);
-        stream = buf + 8;
-    }
+    const ModelInput ib = model_input(in, in_len);
     RawDecoder dec(*lds);
     uint32_t *&kept = kept_scratch<RB>();
     if (!getenv("PZM_NO_STRIPS")) {
@@ -54,14 +43,14 @@ static void run_one(const uint8_t *in, uint64_t in_len, const uint8_t *dict, uin
         dec.strip = kept;
     }
     pzg::StreamResult sr;
-    dec.run(stream, in_len, out, cap, &sr, dict_len ? dict : nullptr, dict_len);
+    dec.run(ib.stream, in_len, out, cap, &sr, dict_len ? dict : nullptr, dict_len);
     r->status = sr.status;
     r->detail0 = sr.detail0;
     r->detail1 = sr.detail1;
     r->adler = sr.adler;
     r->out_len = sr.out_len;
     r->in_used = sr.in_used;
-    free(buf);
+    free(ib.buf);
     free(lds);
 }
 

@@ -8,6 +8,7 @@
 #include <string.h>
 
 #include "../../pure_zlib_amd/csrc/inflate_core.h"
+#include "model_input.h"
 
 struct pzm_result {
     int32_t status;
@@ -25,16 +26,14 @@ static void feed(uint8_t *state, const uint8_t *in, uint64_t in_len, uint32_t fi
     typedef pzg::Decoder<RB, GZ, true, RAW> Dec;
     auto *lds = (pzg::WaveLds<RB> *)aligned_alloc(16, (sizeof(pzg::WaveLds<RB>) + 15u) & ~(size_t)15u);
     memset(lds, 0xA5, sizeof(*lds));  // LDS is not zero-initialised on the device either
-    uint8_t *buf = (uint8_t *)malloc(in_len + 16);
-    memset(buf, 0xEE, in_len + 16);
-    if (in_len) memcpy(buf + 8, in, in_len);
+    const ModelInput ib = model_input(in, in_len);  // (padded, or as PZM_TIGHT_INPUT says)
     Dec dec(*lds);
     pzg::StreamResult sr;
     // the wave's scratch (strips); PZM_NO_STRIPS=1 in the environment: the windows alone
     uint32_t *strip = getenv("PZM_NO_STRIPS") ? nullptr : (uint32_t *)malloc(sizeof(uint32_t) * Dec::STRIP_WORDS);
     if (strip) memset(strip, 0xC3, sizeof(uint32_t) * Dec::STRIP_WORDS);
     dec.strip = strip;
-    dec.run_resume((pzg::ResumeState *)state, (uint32_t *)(state + pzg::ResumeSlot<RB>::IMAGE_OFF), state + pzg::ResumeSlot<RB>::HIST_OFF, buf + 8, in_len,
+    dec.run_resume((pzg::ResumeState *)state, (uint32_t *)(state + pzg::ResumeSlot<RB>::IMAGE_OFF), state + pzg::ResumeSlot<RB>::HIST_OFF, ib.stream, in_len,
                    out, cap, final_input, &sr, chunks);
     r->status = sr.status;
     r->detail0 = sr.detail0;
@@ -44,7 +43,7 @@ static void feed(uint8_t *state, const uint8_t *in, uint64_t in_len, uint32_t fi
     r->in_used = sr.in_used;
     *gz_expect = sr.gz_crc;
     free(strip);
-    free(buf);
+    free(ib.buf);
     free(lds);
 }
 

@@ -7,6 +7,7 @@
 #include <string.h>
 
 #include "../../pure_zlib_amd/csrc/inflate_core.h"
+#include "model_input.h"
 
 struct pzm_result {
     int32_t status;
@@ -17,7 +18,8 @@ struct pzm_result {
 extern "C" {
 
 // One segment (or, with span != 0, one index build: start_bit = end_bit = 0 then, and *npoints gets the points the stream has).  The
-// input is allocated as exactly the aligned dwords that cover it, as the kernel reads it; no scratch: the windows alone, as the kernel.
+// input is allocated as exactly the aligned dwords that cover it, as the kernel reads it (model_input.h: at the end of the block, or
+// where PZM_TIGHT_INPUT says; under ASan + UBSan in tests/test_sanitized_cores.py); no scratch: the windows alone, as the kernel.
 int pzm_seg_decompress(const uint8_t *in, uint64_t in_len, uint32_t start_bit, uint64_t end_bit, const uint8_t *dict, uint32_t dict_len,
                        uint8_t *out, uint64_t cap, uint64_t span, uint64_t *points, uint32_t max_points, uint32_t *npoints, pzm_result *r)
 {
@@ -25,10 +27,7 @@ int pzm_seg_decompress(const uint8_t *in, uint64_t in_len, uint32_t start_bit, u
     static_assert(sizeof(pzg::IndexPoint) == 16, "two 64-bit words per point");
     auto *lds = (pzg::WaveLds<15> *)aligned_alloc(16, (sizeof(pzg::WaveLds<15>) + 15u) & ~(size_t)15u);
     memset(lds, 0xA5, sizeof(*lds));  // LDS is not zero-initialised on the device either
-    const uint64_t mis = (4u - (in_len & 3u)) & 3u;
-    uint8_t *buf = (uint8_t *)malloc(mis + in_len ? mis + in_len : 1);
-    memset(buf, 0xEE, mis);
-    if (in_len) memcpy(buf + mis, in, in_len);
+    const ModelInput ib = model_input(in, in_len, 0, true);
     SegDecoder dec(*lds);
     dec.seg_start = start_bit;
     dec.seg_end = end_bit;
@@ -36,7 +35,7 @@ int pzm_seg_decompress(const uint8_t *in, uint64_t in_len, uint32_t start_bit, u
     dec.idx_cap = max_points;
     dec.idx_span = span;
     pzg::StreamResult sr;
-    dec.run(buf + mis, in_len, out, cap, &sr, dict_len ? dict : nullptr, dict_len);
+    dec.run(ib.stream, in_len, out, cap, &sr, dict_len ? dict : nullptr, dict_len);
     if (npoints) *npoints = dec.idx_n;
     r->status = sr.status;
     r->detail0 = sr.detail0;
@@ -44,7 +43,7 @@ int pzm_seg_decompress(const uint8_t *in, uint64_t in_len, uint32_t start_bit, u
     r->adler = sr.adler;
     r->out_len = sr.out_len;
     r->in_used = sr.in_used;
-    free(buf);
+    free(ib.buf);
     free(lds);
     return 0;
 }

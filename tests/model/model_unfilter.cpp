@@ -3,8 +3,11 @@
 // without a GPU: the 64 lanes of a group are an array here, a step a loop over them.  The destination has 64 guard bytes on both
 // sides, the input none at all beyond the aligned dwords that hold it, and a guard that changed is the call's return value.
 // Never linked into libpzg.so; the product has no CPU path.
-// With -DPZU_MAIN it is a program of its own (for a sanitizer build): model_unfilter [SEED] runs seeded images of every bpp at the
-// edge shapes against a byte-by-byte unfilter of its own.
+// Built with AddressSanitizer (tests/test_sanitized_cores.py builds it so with tests/cxx/san_unfilter.cpp and runs every case of
+// tests/pngcases.py) the destination is instead a heap block of exactly the aligned dwords that hold the image's extent, which the
+// core may read whole: the sanitizer is the guard then, for reads as well as writes.
+// With -DPZU_MAIN it is a program of its own: model_unfilter [SEED] runs seeded images of every bpp at the edge shapes against a
+// byte-by-byte unfilter of its own.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -62,17 +65,30 @@ int pzu_unfilter(const uint8_t *src, uint64_t src_len, uint32_t mis, uint8_t *ds
                  uint32_t row_bytes, uint32_t height, uint32_t bpp, int32_t *sd)
 {
     Input inp(src, src_len, mis);
-    Guarded out((size_t)dst_bytes);
-    if (dst_bytes) memcpy(out.p(), dst, (size_t)dst_bytes);
     int32_t status = -1;
     uint32_t d0 = 0, d1 = 0;
+#if defined(__SANITIZE_ADDRESS__)
+    // [lo, hi) of the caller's bytes: the aligned dwords that hold [dst_off, dst_off + (height - 1) stride + row_bytes), cut to what
+    // the caller has (an illegal stride: nothing may be touched, whatever the extent would be)
+    const uint64_t extent = height && row_bytes && stride >= row_bytes ? (uint64_t)(height - 1u) * stride + row_bytes : 0u;
+    const uint64_t lo = dst_off & ~(uint64_t)3u, end = (dst_off + extent + 3u) & ~(uint64_t)3u, hi = !extent ? lo : end < dst_bytes ? end : dst_bytes;
+    uint8_t *block = (uint8_t *)malloc(hi > lo ? (size_t)(hi - lo) : 16), *at = hi > lo ? block : block + 16;  // (malloc: 16-byte aligned)
+    if (hi > lo) memcpy(at, dst + lo, (size_t)(hi - lo));
+    pzg::Unfilter::image(inp.in, src_len, at + (dst_off - lo), stride, row_bytes, height, bpp, &status, &d0, &d1);
+    if (hi > lo) memcpy(dst + lo, at, (size_t)(hi - lo));
+    free(block);
+    const bool ok = true;
+#else
+    Guarded out((size_t)dst_bytes);
+    if (dst_bytes) memcpy(out.p(), dst, (size_t)dst_bytes);
     pzg::Unfilter::image(inp.in, src_len, out.p() + dst_off, stride, row_bytes, height, bpp, &status, &d0, &d1);
+    const bool ok = out.ok();
+    if (ok && dst_bytes) memcpy(dst, out.p(), (size_t)dst_bytes);
+#endif
     sd[0] = status;
     sd[1] = (int32_t)d0;
     sd[2] = (int32_t)d1;
-    if (!out.ok()) return 1;
-    if (dst_bytes) memcpy(dst, out.p(), (size_t)dst_bytes);
-    return 0;
+    return ok ? 0 : 1;
 }
 }
 
