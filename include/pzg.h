@@ -91,7 +91,8 @@ extern "C" {
                                       * not the Adler-32 of the dictionary supplied for it (d1) */
 #define PZG_E_SEGMENT 21  /* segments only: the blocks do not end at end_bit. d0 = 1 final block came first, 2 a block ran past; d1 = bit reached */
 #define PZG_E_FILTER 23  /* (0.5) pzg_unfilter_many only: row d0 has filter byte d1 (> 4).  d0 = 0xffffffff: the image's bpp (d1) or its
-                            stride is not legal -- device arrays only, the host-pointer form refuses the call */
+                            stride is not legal -- device arrays only, the host-pointer form refuses the call.  pzg_adam7_many: only
+                            the latter, d1 = the image's pixel_bits */
 #define PZG_E_SCAN 22  /* pzg_index_scan only: the chain of blocks did not reach the final block.
                           d0 = the status the chain's last segment met (0: a dead wave),
                           d1 = low 32 bits of that segment's start bit.
@@ -496,6 +497,46 @@ PZG_API int pzg_unfilter_many(pzg_ctx *ctx,
         const uint8_t *src_base, const uint64_t *src_off, const uint64_t *src_len,
         uint8_t *dst_base, const uint64_t *dst_off, const uint64_t *dst_stride,
         const uint32_t *row_bytes, const uint32_t *height, const uint8_t *bpp,
+        int32_t *status, uint32_t *detail,   /* detail: 2n, or NULL */
+        uint32_t n, uint32_t flags);         /* 0, PZG_DEVICE_PTRS, PZG_DEVICE_PTRS | PZG_ASYNC */
+
+/*
+ * pzg_adam7_many (0.5): EXTENSION -- Adam7 deinterlacing (PNG specification section 8.2), what follows the unfiltering of an
+ * interlaced PNG: the seven reduced images of each of n images woven into the image, all n in one launch, the rows of an image
+ * spread over several wavefronts.
+ *   source i    the seven reduced images, unfiltered and without filter bytes, dense and back to back in pass order at
+ *               src_base + src_off[i].  Pass p holds the pixels (x0 + j dx, y0 + k dy) of the image:
+ *                   pass  1  2  3  4  5  6  7
+ *                   x0    0  4  0  2  0  1  0
+ *                   y0    0  0  4  0  2  0  1
+ *                   dx    8  8  4  4  2  2  1
+ *                   dy    8  8  8  4  4  2  2
+ *               as ph = ceil((height[i] - y0) / dy) rows of prb = ceil(pw * pixel_bits[i] / 8) bytes, pw = ceil((width[i] - x0) / dx);
+ *               a pass with pw == 0 or ph == 0 takes no bytes.  The extent is a function of (width, height, pixel_bits) alone --
+ *               there is no src_len -- and it is where seven pzg_unfilter_many jobs deliver with dst_stride = row_bytes = prb.
+ *   pixel_bits  the bits of a pixel: 1, 2, 4, 8, 16, 24, 32, 48 or 64.  Pixels are moved as bits and bytes, nothing is swapped or
+ *               expanded.  Below 8 bits they are packed with the leftmost pixel in the high bits, in each pass row and in each
+ *               row delivered; the unused low bits of a delivered row's last byte are written as 0.
+ *   delivery    row y of the image, ceil(width[i] * pixel_bits[i] / 8) bytes, at dst_base + dst_off[i] + y * dst_stride[i].  The bytes
+ *               between that and the stride and everything outside the extents are untouched.  The dst extents overlap neither
+ *               each other nor src.
+ *   status[i]   PZG_OK; width or height of 0: PZG_OK, nothing read or written.
+ *   detail      2n words (d0, d1 per image), or NULL: 0, 0 of a PZG_OK image.
+ * flags: as for pzg_unfilter_many.  0 -- every pointer is host memory: the call stages src, the arrays and dst's extents through
+ * the context's arenas and returns when dst and status are filled; PZG_DEVICE_PTRS -- every pointer is device memory, the launch
+ * goes on the context's stream (pzg_set_stream) in call order, and with PZG_ASYNC as well the call only enqueues:
+ * pzg_decompress_many, pzg_unfilter_many (the pass jobs), pzg_adam7_many and pzg_sync chain without a host round trip.
+ * pzg_last_kernel_ms reports the launch.
+ * PZG_RC_BAD_ARG: n == 0, any other flag, a null array, a context of several devices; with host pointers also, of an image that has
+ * pixels, a pixel_bits outside the list, a stride below the row's bytes and a width or height of 2^31 or more.  Device arrays are
+ * not read by the host: there such an image gets PZG_E_FILTER with d0 = 0xffffffff (d1 = its pixel_bits) and nothing of it is read
+ * or written.
+ * Offsets and strides are 64-bit.  Nothing is read but the aligned dwords that hold bytes of the image's source extent.
+ */
+PZG_API int pzg_adam7_many(pzg_ctx *ctx,
+        const uint8_t *src_base, const uint64_t *src_off,
+        uint8_t *dst_base, const uint64_t *dst_off, const uint64_t *dst_stride,
+        const uint32_t *width, const uint32_t *height, const uint8_t *pixel_bits,
         int32_t *status, uint32_t *detail,   /* detail: 2n, or NULL */
         uint32_t n, uint32_t flags);         /* 0, PZG_DEVICE_PTRS, PZG_DEVICE_PTRS | PZG_ASYNC */
 

@@ -10,7 +10,8 @@ Only what the hot path needs lives here:
   zip.py     ZIP archives read and tested in one launch (raw DEFLATE members, sizes and CRC-32s from the central directory)
   indexed.py ONE large stream: an index of access points, every segment its own wavefront, reads at any offset
   gzfile.py  a gzip FILE of many members (BGZF, WARC, concatenated .gz): members found on the device, a wavefront per member
-  png.py     PNG images in batches: one decode launch, one unfilter launch (pzg_unfilter_many), the pixels in one copy
+  png.py     PNG images in batches: one decode launch, one unfilter launch (pzg_unfilter_many), the pixels in one copy;
+             Adam7 images with adam7=True, deinterlaced on the device (pzg_adam7_many)
   cxx/       the same module mirror in C++ (header-only)
 
 There is no CPU fallback: importing works anywhere, computing needs libpzg.so and a gfx950 device.

@@ -31,7 +31,7 @@ E_GZIP_HEADER = 18  # PZG_GZIP only (extension)
 E_GZIP_ISIZE = 19
 E_DICT = 20  # pzg_decompress_many_dict only (extension)
 E_SCAN = 22  # pzg_index_scan, pzg_index_scan_many only (extension): the chain of blocks did not reach the final block
-E_FILTER = 23  # pzg_unfilter_many only (extension): row detail[0] has the filter byte detail[1] (> 4)
+E_FILTER = 23  # pzg_unfilter_many, pzg_adam7_many only (extension): row detail[0] has the filter byte detail[1] (> 4)
 E_SEGMENT = 21  # pzg_decompress_many_segments only (extension): the blocks do not end at end_bit
 DEC_NEED_INPUT = 101  # pzg_decoder_feed: NeedMore
 DEC_OUT_FULL = 102    # pzg_decoder_feed: this call's output room is used up
@@ -56,7 +56,7 @@ SYMBOLS = [
     "pzg_decoder_create", "pzg_decoder_create_format", "pzg_decoder_destroy", "pzg_decoder_reset", "pzg_decoder_feed", "pzg_decoder_last_feed_ms", "pzg_shutdown", "pzg_set_stream", "pzg_reset_stream", "pzg_set_option", "pzg_sync", "pzg_decompress_many", "pzg_decompress",
     "pzg_adler32", "pzg_error_message", "pzg_last_kernel_ms", "pzg_strerror", "pzg_last_error", "pzg_version",
     "pzg_index_build", "pzg_decompress_many_segments", "pzg_index_scan", "pzg_index_scan_many", "pzg_gzip_find_members", "pzg_gzip_layout",
-    "pzg_unfilter_many",
+    "pzg_unfilter_many", "pzg_adam7_many",
 ]
 
 
@@ -138,6 +138,9 @@ def lib():
     if hasattr(L, "pzg_unfilter_many"):
         L.pzg_unfilter_many.argtypes = [C.c_void_p, vp, u64p, u64p, vp, u64p, u64p, u32p, u32p, vp, i32p, u32p, C.c_uint32, C.c_uint32]
         L.pzg_unfilter_many.restype = C.c_int
+    if hasattr(L, "pzg_adam7_many"):
+        L.pzg_adam7_many.argtypes = [C.c_void_p, vp, u64p, vp, u64p, u64p, u32p, u32p, vp, i32p, u32p, C.c_uint32, C.c_uint32]
+        L.pzg_adam7_many.restype = C.c_int
     L.pzg_decompress_many_sharded.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
     L.pzg_decompress_many_sharded.restype = C.c_int
     L.pzg_decoder_create.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]

@@ -47,6 +47,7 @@
 #include "pzg_launch.h"
 #include "scan_core.h"  // (ScanStream, ScanResult: the tables of pzg_index_scan_many)
 #include "pzg_unfilter_kernel.h"  // (unfilter_kernel and its launcher; unfilter_core.h: its statuses, and what it takes for a legal bpp)
+#include "pzg_adam7_kernel.h"     // (adam7_kernel and its launcher; adam7_core.h: its statuses, a legal geometry, an image's source extent)
 
 namespace {
 
@@ -1887,6 +1888,109 @@ int pzg_unfilter_many(pzg_ctx *ctx, const uint8_t *src_base, const uint64_t *src
             for (uint32_t r = 0; r < rows; ++r) {
                 const uint64_t at = dst_off[i] + (uint64_t)r * dst_stride[i];
                 memcpy(dst_base + at, ln.h_out[0].p + (at - d_lo), row_bytes[i]);
+            }
+        }
+        return PZG_RC_OK;
+    });
+}
+
+// Adam7 deinterlacing (adam7_core.h): the two forms of pzg_unfilter_many.  The host-pointer form stages the span of src that holds the
+// images' passes, the arrays and the span of dst that holds the extents, and copies the rows of the images -- nothing else -- from the
+// staged span into the caller's dst.
+int pzg_adam7_many(pzg_ctx *ctx, const uint8_t *src_base, const uint64_t *src_off, uint8_t *dst_base, const uint64_t *dst_off, const uint64_t *dst_stride,
+                   const uint32_t *width, const uint32_t *height, const uint8_t *pixel_bits, int32_t *status, uint32_t *detail, uint32_t n, uint32_t flags)
+{
+    static_assert(pzg::Adam7::ST_FILTER == PZG_E_FILTER && pzg::Adam7::ST_OK == PZG_OK, "the core's statuses are the header's");
+    if (!ctx_live(ctx) || n == 0) return PZG_RC_BAD_ARG;
+    if ((flags & ~(PZG_DEVICE_PTRS | PZG_ASYNC)) || ((flags & PZG_ASYNC) && !(flags & PZG_DEVICE_PTRS))) return PZG_RC_BAD_ARG;
+    if (ctx->shards.size() != 1) return PZG_RC_BAD_ARG;
+    if (!src_base || !src_off || !dst_base || !dst_off || !dst_stride || !width || !height || !pixel_bits || !status) return PZG_RC_BAD_ARG;
+    Shard &sh = *ctx->shards[0];
+    if (flags & PZG_DEVICE_PTRS)
+        return guarded(ctx, "pzg_adam7_many", [&]() -> int {
+            std::lock_guard<std::mutex> g(sh.mu);
+            HIP_TRY(ctx, hipSetDevice(sh.device));
+            pzg::Adam7Args a{src_base, src_off, dst_base, dst_off, dst_stride, width, height, pixel_bits, status, detail, n};
+            HIP_TRY(ctx, hipEventRecord(sh.ev0, sh.stream));
+            HIP_TRY(ctx, pzg::launch_adam7(a, sh.stream));
+            HIP_TRY(ctx, hipEventRecord(sh.ev1, sh.stream));
+            sh.timed = true;
+            sh.last_was_host = false;
+            if (!(flags & PZG_ASYNC)) HIP_TRY(ctx, hipStreamSynchronize(sh.stream));
+            return PZG_RC_OK;
+        });
+    // host pointers: the spans, and what the device form leaves to the kernel
+    uint64_t s_lo = ~0ull, s_hi = 0, d_lo = ~0ull, d_hi = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (width[i] == 0u || height[i] == 0u) continue;
+        if (!pzg::Adam7::geometry_ok(dst_stride[i], width[i], height[i], pixel_bits[i])) return PZG_RC_BAD_ARG;
+        const uint64_t d_end = dst_off[i] + (uint64_t)(height[i] - 1u) * dst_stride[i] + pzg::Adam7::bytes_of(width[i], pixel_bits[i]);
+        d_lo = std::min(d_lo, dst_off[i]);
+        d_hi = std::max(d_hi, d_end);
+        s_lo = std::min(s_lo, src_off[i]);
+        s_hi = std::max(s_hi, src_off[i] + pzg::Adam7::src_extent(width[i], height[i], pixel_bits[i]));
+    }
+    if (d_lo > d_hi) {  // nothing but empty images
+        for (uint32_t i = 0; i < n; ++i) status[i] = PZG_OK;
+        if (detail) memset(detail, 0, 8 * (size_t)n);
+        return PZG_RC_OK;
+    }
+    return guarded(ctx, "pzg_adam7_many", [&]() -> int {
+        LaneCall call(ctx, sh);
+        if (call.rc != PZG_RC_OK) return call.rc;
+        Lane &ln = call.ln;
+        hipStream_t st = call.st;
+        int rc;
+        // the spans keep their places modulo 16: a row is fetched and stored at the alignment the caller gave it
+        const size_t s_skew = (size_t)((uintptr_t)(src_base + s_lo) & 15u), d_skew = (size_t)((uintptr_t)(dst_base + d_lo) & 15u);
+        const size_t s_bytes = (size_t)(s_hi - s_lo), d_bytes = (size_t)(d_hi - d_lo);
+        const size_t row8 = pad256(8 * (size_t)n), row4 = pad256(4 * (size_t)n);
+        const size_t m_in = 3 * row8 + 2 * row4 + pad256(n), m_all = m_in + row4 + pad256(8 * (size_t)n);
+        if ((rc = arena_reserve(ctx, ln.d_in[0], s_bytes + 64)) != PZG_RC_OK) return rc;
+        if ((rc = arena_reserve(ctx, ln.d_out[0], d_bytes + 64)) != PZG_RC_OK) return rc;
+        if ((rc = arena_reserve(ctx, ln.d_meta[0], m_all)) != PZG_RC_OK) return rc;
+        if ((rc = pinned_reserve(ctx, ln.h_meta[0], m_all)) != PZG_RC_OK) return rc;
+        if ((rc = pinned_reserve(ctx, ln.h_out[0], d_bytes + 64)) != PZG_RC_OK) return rc;
+        uint8_t *hm = ln.h_meta[0].p, *dm = (uint8_t *)ln.d_meta[0].p;
+        uint64_t *h_soff = (uint64_t *)(void *)hm, *h_doff = (uint64_t *)(void *)(hm + row8);
+        for (uint32_t i = 0; i < n; ++i) {
+            const bool empty = width[i] == 0u || height[i] == 0u;
+            h_soff[i] = empty ? 0u : src_off[i] - s_lo;
+            h_doff[i] = empty ? 0u : dst_off[i] - d_lo;
+        }
+        memcpy(hm + 2 * row8, dst_stride, 8 * (size_t)n);
+        memcpy(hm + 3 * row8, width, 4 * (size_t)n);
+        memcpy(hm + 3 * row8 + row4, height, 4 * (size_t)n);
+        memcpy(hm + 3 * row8 + 2 * row4, pixel_bits, n);
+        HIP_TRY(ctx, hipMemcpyAsync(dm, hm, m_in, hipMemcpyHostToDevice, st));
+        if (s_bytes) HIP_TRY(ctx, hipMemcpyAsync((uint8_t *)ln.d_in[0].p + s_skew, src_base + s_lo, s_bytes, hipMemcpyHostToDevice, st));
+        pzg::Adam7Args a{};
+        a.src_base = (const uint8_t *)ln.d_in[0].p + s_skew;
+        a.src_off = (const uint64_t *)(void *)dm;
+        a.dst_base = (uint8_t *)ln.d_out[0].p + d_skew;
+        a.dst_off = (const uint64_t *)(void *)(dm + row8);
+        a.dst_stride = (const uint64_t *)(void *)(dm + 2 * row8);
+        a.width = (const uint32_t *)(void *)(dm + 3 * row8);
+        a.height = (const uint32_t *)(void *)(dm + 3 * row8 + row4);
+        a.pixel_bits = dm + 3 * row8 + 2 * row4;
+        a.status = (int32_t *)(void *)(dm + m_in);
+        a.detail = (uint32_t *)(void *)(dm + m_in + row4);
+        a.n = n;
+        HIP_TRY(ctx, call.begin_timed());
+        HIP_TRY(ctx, pzg::launch_adam7(a, st));
+        HIP_TRY(ctx, call.end_timed());
+        HIP_TRY(ctx, hipMemcpyAsync(hm + m_in, dm + m_in, m_all - m_in, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipMemcpyAsync(ln.h_out[0].p, a.dst_base, d_bytes, hipMemcpyDeviceToHost, st));
+        if ((rc = call.finish()) != PZG_RC_OK) return rc;
+        const int32_t *h_status = (const int32_t *)(const void *)(hm + m_in);
+        memcpy(status, h_status, 4 * (size_t)n);
+        if (detail) memcpy(detail, hm + m_in + row4, 8 * (size_t)n);
+        for (uint32_t i = 0; i < n; ++i) {  // the rows the kernel delivered
+            if (width[i] == 0u || height[i] == 0u || h_status[i] != PZG_OK) continue;
+            const uint64_t rb = pzg::Adam7::bytes_of(width[i], pixel_bits[i]);
+            for (uint32_t r = 0; r < height[i]; ++r) {
+                const uint64_t at = dst_off[i] + (uint64_t)r * dst_stride[i];
+                memcpy(dst_base + at, ln.h_out[0].p + (at - d_lo), rb);
             }
         }
         return PZG_RC_OK;

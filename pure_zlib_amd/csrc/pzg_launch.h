@@ -194,6 +194,20 @@ struct UnfilterArgs {
     uint32_t n;
 };
 
+// Adam7 deinterlacing (pzg_adam7_kernel.h, adam7_core.h; compiled with pzg_api.cpp): the rows of an image over the grid's y.  Every
+// pointer is device memory.
+struct Adam7Args {
+    const uint8_t *src_base;
+    const uint64_t *src_off;  // n
+    uint8_t *dst_base;
+    const uint64_t *dst_off, *dst_stride;  // n
+    const uint32_t *width, *height;        // n
+    const uint8_t *pixel_bits;             // n
+    int32_t *status;                       // n
+    uint32_t *detail;                      // 2n or null
+    uint32_t n;
+};
+
 // partials: 3 * 4 * ceil(max_waves / 4) uint32 of device scratch
 hipError_t launch_adler32(const uint8_t *buf, uint64_t len, uint32_t init, uint32_t *partials, uint32_t max_waves,
                           uint32_t *out, hipStream_t stream);

@@ -9,10 +9,18 @@ checks their CRC-32s with the system's zlib; nothing is inflated on the CPU.  De
     read_png_many(blobs_or_paths)  -> [PngImage, or the DecompressionError / ValueError / NotImplementedError of that image]
     read_png(blob_or_path)         -> PngImage                  (raises)
     test_png_many(blobs_or_paths)  -> [(index_or_name, problem)]   (empty: every image is sound)
-    python -m pure_zlib_amd.png -t A.png B.png ...
+    python -m pure_zlib_amd.png -t [--adam7] A.png B.png ...
 
-Colour types 0, 2, 3, 4 and 6 at their legal bit depths, not interlaced (an Adam7 image is NotImplementedError, for that image
-only).  `data` is the samples as the file stores them -- no palette expansion, no gamma, no alpha handling: a viewer's work.
+Colour types 0, 2, 3, 4 and 6 at their legal bit depths.  `data` is the samples as the file stores them -- no palette expansion, no
+bit-depth expansion, no gamma, no alpha handling: a viewer's work.
+
+Adam7-interlaced images are read with adam7=True (--adam7); without it such an image is NotImplementedError, for that image only,
+and nothing else changes.  An interlaced image's stream is its seven reduced images, each filtered on its own, so its exact decoded
+size is the sum of ph * (1 + prb) over the passes that have pixels; each such pass is one job of a second pzg_unfilter_many launch
+-- its src_off inside the image's decoded stream, its exact size as src_len, delivered dense into a device scratch -- and one
+pzg_adam7_many launch behind it on the same stream weaves the passes into the pixel buffer (or into device_out at the caller's
+offsets and strides).  Still one sync and one copy out; nothing is deinterlaced on the host, and `data` is what a non-interlaced
+file of the same pixels gives.  A batch without interlaced images issues exactly the two launches above.
 """
 import os
 import struct
@@ -58,11 +66,26 @@ def _format_error(msg: str) -> DecompressionError:
     return DecompressionError("FormatError", msg, _ffi.E_FILTER)
 
 
-def _parse(name: str, blob: bytes) -> Tuple[PngImage, bytes]:
-    """(the image without its data, its IDAT payloads joined); raises ValueError / NotImplementedError naming the image."""
+# Adam7 (PNG specification 8.2): (x0, y0, dx, dy) of the passes 1 .. 7
+_ADAM7 = ((0, 0, 8, 8), (4, 0, 8, 8), (0, 4, 4, 8), (2, 0, 4, 4), (0, 2, 2, 4), (1, 0, 2, 2), (0, 1, 1, 2))
+
+
+def _passes(img: PngImage) -> List[Tuple[int, int, int]]:
+    """[(pass 1 .. 7, its rows, the bytes of one)] of the passes of an interlaced image that have pixels."""
+    out, bits = [], img.channels * img.bit_depth
+    for p, (x0, y0, dx, dy) in enumerate(_ADAM7):
+        pw, ph = -(-(img.width - x0) // dx), -(-(img.height - y0) // dy)
+        if pw > 0 and ph > 0:
+            out.append((p + 1, ph, (pw * bits + 7) // 8))
+    return out
+
+
+def _parse(name: str, blob: bytes, adam7: bool = False) -> Tuple[PngImage, bytes, bool]:
+    """(the image without its data, its IDAT payloads joined, whether it is interlaced); raises ValueError / NotImplementedError
+    naming the image."""
     if blob[:8] != SIGNATURE:
         raise ValueError("%s: not a PNG file (bad signature)" % name)
-    at, img, idat, seen_idat, idat_closed, palette, trns = 8, None, [], False, False, None, None
+    at, img, idat, seen_idat, idat_closed, palette, trns, laced = 8, None, [], False, False, None, None, False
     while True:
         if at + 12 > len(blob):
             raise ValueError("%s: file ends inside a chunk (no IEND)" % name)
@@ -85,8 +108,9 @@ def _parse(name: str, blob: bytes) -> Tuple[PngImage, bytes]:
                 raise ValueError("%s: colour type %d with bit depth %d is not a PNG image type" % (name, ctype, depth))
             if w == 0 or h == 0 or w >> 31 or h >> 31 or comp != 0 or filt != 0 or lace > 1:
                 raise ValueError("%s: bad IHDR (size %d x %d, compression %d, filter %d, interlace %d)" % (name, w, h, comp, filt, lace))
-            if lace == 1:
-                raise NotImplementedError("%s: Adam7-interlaced images are not supported" % name)
+            if lace == 1 and not adam7:
+                raise NotImplementedError("%s: Adam7-interlaced images are read with adam7=True (--adam7) only" % name)
+            laced = lace == 1
             img = PngImage(w, h, ctype, depth, None, None, None)
             if img.row_bytes >> 32:
                 raise ValueError("%s: a row of %d bytes" % (name, img.row_bytes))
@@ -112,7 +136,7 @@ def _parse(name: str, blob: bytes) -> Tuple[PngImage, bytes]:
     if img.color_type == 3 and palette is None:
         raise ValueError("%s: a palette image without PLTE" % name)
     img.palette, img.trns = palette, trns
-    return img, b"".join(idat)
+    return img, b"".join(idat), laced
 
 
 def _shape(img: PngImage, flat: np.ndarray) -> np.ndarray:
@@ -131,19 +155,22 @@ def _load(src) -> Tuple[Optional[str], bytes]:
 
 
 def read_png_many(blobs_or_paths: Sequence[Union[str, os.PathLike, bytes, bytearray, memoryview]], ctx: Optional[Context] = None,
-                  device_out: Optional[Tuple[int, Sequence[int], Sequence[int]]] = None) -> List[Union[PngImage, Exception]]:
+                  device_out: Optional[Tuple[int, Sequence[int], Sequence[int]]] = None, adam7: bool = False) -> List[Union[PngImage, Exception]]:
     """Every image of the batch, or in its place the exception that read_png would raise for it: a bad image never disturbs its
     neighbours.  device_out = (ptr, offsets, strides): the rows of image i land at ptr + offsets[i] + r * strides[i] in device
-    memory of the caller's (a torch tensor's data_ptr()), nothing is copied out and `data` is None."""
+    memory of the caller's (a torch tensor's data_ptr()), nothing is copied out and `data` is None.  adam7: Adam7-interlaced
+    images are read too, deinterlaced on the device (without it each is NotImplementedError)."""
     import torch
     results: List[Union[PngImage, Exception, None]] = [None] * len(blobs_or_paths)
-    names, good = [], []  # good: (index, image, stream)
+    names, good, laced = [], [], []  # good: (index, image, stream); laced: the interlaced ones, as (place in good, its passes)
     for k, src in enumerate(blobs_or_paths):
         name = "#%d" % k
         try:
             path, blob = _load(src)
             name = path or name
-            img, z = _parse(name, blob)
+            img, z, lace = _parse(name, blob, adam7)
+            if lace:
+                laced.append((len(good), _passes(img)))
             good.append((k, img, z))
         except (ValueError, NotImplementedError, OSError) as e:
             results[k] = e
@@ -157,6 +184,8 @@ def read_png_many(blobs_or_paths: Sequence[Union[str, os.PathLike, bytes, bytear
     height = np.array([i.height for _k, i, _z in good], dtype=np.uint32)
     bpp = np.array([i.bpp for _k, i, _z in good], dtype=np.uint8)
     dec_cap = height.astype(np.uint64) * (row_bytes.astype(np.uint64) + np.uint64(1))
+    for j, passes in laced:  # the seven reduced images, each row with its filter byte
+        dec_cap[j] = sum(ph * (1 + prb) for _p, ph, prb in passes)
     pix = height.astype(np.uint64) * row_bytes.astype(np.uint64)
     in_off, dec_off, pix_off = (np.zeros(n, dtype=np.uint64) for _ in range(3))
     in_off[1:] = np.cumsum(pad(in_len))[:-1]
@@ -180,19 +209,63 @@ def read_png_many(blobs_or_paths: Sequence[Union[str, os.PathLike, bytes, bytear
             ain.a[int(in_off[j]):int(in_off[j]) + len(z)] = np.frombuffer(z, dtype=np.uint8)
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8)).to(dev)  # noqa: E731
         d_in = up(ain.a[:tot_in])
-        d_meta = [up(a) for a in (in_off, in_len, dec_off, dec_cap, pix_off, stride, row_bytes, height, bpp)]
+        plain_height = height.copy()
+        for j, _ps in laced:
+            plain_height[j] = 0  # (no rows: the first unfilter launch neither reads nor writes an interlaced image)
+        d_meta = [up(a) for a in (in_off, in_len, dec_off, dec_cap, pix_off, stride, row_bytes, plain_height, bpp)]
         d_dec = torch.empty(tot_dec, dtype=torch.uint8, device=dev)
         d_pix = torch.empty(tot_pix, dtype=torch.uint8, device=dev) if device_out is None else None
         d_out_len = torch.zeros(8 * n, dtype=torch.uint8, device=dev)
         d_status = torch.zeros(2 * 4 * n, dtype=torch.uint8, device=dev)   # the decode's, the unfilter's
         d_detail = torch.zeros(2 * 8 * n, dtype=torch.uint8, device=dev)
+        if laced:
+            # every pass that has pixels is one unfilter job, from its place in the image's decoded stream into a scratch of dense
+            # passes; then one launch weaves each image's passes into its rows
+            jobs, scr_off, scr_at = [], [], 0  # jobs: (src_off, src_len, dst_off, row bytes, rows, bpp)
+            for j, passes in laced:
+                scr_off.append(scr_at)
+                s_at = int(dec_off[j])
+                for _p, ph, prb in passes:
+                    jobs.append((s_at, ph * (1 + prb), scr_at, prb, ph, int(bpp[j])))
+                    s_at += ph * (1 + prb)
+                    scr_at += ph * prb
+                scr_at = (scr_at + 15) & ~15
+            m, jj = len(jobs), [j for j, _ps in laced]
+            col = lambda c, t: np.array([job[c] for job in jobs], dtype=t)  # noqa: E731
+            d_jobs = [up(a) for a in (col(0, np.uint64), col(1, np.uint64), col(2, np.uint64), col(3, np.uint64), col(3, np.uint32), col(4, np.uint32),
+                                      col(5, np.uint8), np.array(scr_off, dtype=np.uint64), pix_off[jj], stride[jj],
+                                      np.array([good[j][1].width for j in jj], dtype=np.uint32), height[jj],
+                                      np.array([good[j][1].channels * good[j][1].bit_depth for j in jj], dtype=np.uint8))]
+            d_scr = torch.empty(scr_at + 16, dtype=torch.uint8, device=dev)
+            d_jstatus = torch.zeros(4 * m, dtype=torch.uint8, device=dev)   # the pass jobs'
+            d_jdetail = torch.zeros(8 * m, dtype=torch.uint8, device=dev)
+            d_astatus = torch.zeros(4 * len(jj), dtype=torch.uint8, device=dev)  # the deinterlacing's
         torch.cuda.synchronize(dev)
         p = [t.data_ptr() for t in d_meta]
         ctx.decompress_many_device(d_in.data_ptr(), p[0], p[1], d_dec.data_ptr(), p[2], p[3], d_out_len.data_ptr(), d_status.data_ptr(),
                                    d_detail.data_ptr(), 0, 0, n, sync=False)
-        ctx.unfilter_many_device(d_dec.data_ptr(), p[2], d_out_len.data_ptr(), out_ptr if device_out is not None else d_pix.data_ptr(), p[4], p[5],
-                                 p[6], p[7], p[8], d_status.data_ptr() + 4 * n, d_detail.data_ptr() + 8 * n, n, sync=False)
+        pix_ptr = out_ptr if device_out is not None else d_pix.data_ptr()
+        if len(laced) < n:  # (a batch of interlaced images only has nothing for this launch)
+            ctx.unfilter_many_device(d_dec.data_ptr(), p[2], d_out_len.data_ptr(), pix_ptr, p[4], p[5], p[6], p[7], p[8], d_status.data_ptr() + 4 * n,
+                                     d_detail.data_ptr() + 8 * n, n, sync=False)
+        if laced:
+            q = [t.data_ptr() for t in d_jobs]
+            ctx.unfilter_many_device(d_dec.data_ptr(), q[0], q[1], d_scr.data_ptr(), q[2], q[3], q[4], q[5], q[6], d_jstatus.data_ptr(),
+                                     d_jdetail.data_ptr(), m, sync=False)
+            ctx.adam7_many_device(d_scr.data_ptr(), q[7], pix_ptr, q[8], q[9], q[10], q[11], q[12], d_astatus.data_ptr(), 0, len(jj), sync=False)
         ctx.sync()
+        pass_error = {}  # place in good -> what its passes and its deinterlacing say, the first pass in pass order first
+        if laced:
+            jstatus, jdetail = d_jstatus.cpu().numpy().view(np.int32), d_jdetail.cpu().numpy().view(np.uint32).reshape(m, 2)
+            astatus = d_astatus.cpu().numpy().view(np.int32)
+            at = 0
+            for i, (j, passes) in enumerate(laced):
+                for t, (pno, _ph, _prb) in enumerate(passes):
+                    if j not in pass_error and int(jstatus[at + t]) != _ffi.OK:
+                        pass_error[j] = (pno, int(jstatus[at + t]), int(jdetail[at + t, 0]), int(jdetail[at + t, 1]))
+                if j not in pass_error and int(astatus[i]) != _ffi.OK:
+                    pass_error[j] = (0, int(astatus[i]), 0, 0)
+                at += len(passes)
         out_len = d_out_len.cpu().numpy().view(np.uint64)
         status = d_status.cpu().numpy().view(np.int32).reshape(2, n)
         detail = d_detail.cpu().numpy().view(np.uint32).reshape(2, n, 2)
@@ -208,6 +281,12 @@ def read_png_many(blobs_or_paths: Sequence[Union[str, os.PathLike, bytes, bytear
             results[k] = DecompressionError(e.constructor, "%s: %s" % (name, e.message), e.status, e.detail)
         elif int(out_len[j]) != int(dec_cap[j]):
             results[k] = _format_error("%s: not enough image data" % name)
+        elif j in pass_error:
+            pno, pst, d0, d1 = pass_error[j]
+            if pno and pst == _ffi.E_FILTER:
+                results[k] = DecompressionError("FormatError", "%s: pass %d: row %d has filter type %d" % (name, pno, d0, d1), pst, (d0, d1))
+            else:
+                results[k] = _format_error("%s: the image's passes could not be put together" % name)
         elif ust == _ffi.E_FILTER:
             results[k] = DecompressionError("FormatError", "%s: row %d has filter type %d" % (name, int(detail[1, j, 0]), int(detail[1, j, 1])),
                                             ust, (int(detail[1, j, 0]), int(detail[1, j, 1])))
@@ -221,18 +300,18 @@ def read_png_many(blobs_or_paths: Sequence[Union[str, os.PathLike, bytes, bytear
     return results
 
 
-def read_png(blob_or_path, ctx: Optional[Context] = None) -> PngImage:
+def read_png(blob_or_path, ctx: Optional[Context] = None, adam7: bool = False) -> PngImage:
     """One image.  Raises what read_png_many would put in its place."""
-    r = read_png_many([blob_or_path], ctx)[0]
+    r = read_png_many([blob_or_path], ctx, adam7=adam7)[0]
     if isinstance(r, Exception):
         raise r
     return r
 
 
-def test_png_many(blobs_or_paths, ctx: Optional[Context] = None) -> List[Tuple[Union[int, str], str]]:
+def test_png_many(blobs_or_paths, ctx: Optional[Context] = None, adam7: bool = False) -> List[Tuple[Union[int, str], str]]:
     """What `pngcheck` does for a batch: [(index or path, problem)] for every image read_png would refuse."""
     out = []
-    for k, (src, r) in enumerate(zip(blobs_or_paths, read_png_many(blobs_or_paths, ctx))):
+    for k, (src, r) in enumerate(zip(blobs_or_paths, read_png_many(blobs_or_paths, ctx, adam7=adam7))):
         if isinstance(r, Exception):
             out.append((k if isinstance(src, (bytes, bytearray, memoryview)) else os.fspath(src), str(r)))
     return out
@@ -244,12 +323,15 @@ test_png_many.__test__ = False  # (not a pytest test, whatever imports it)
 def main(argv=None) -> int:
     argv = sys.argv[1:] if argv is None else list(argv)
     if len(argv) >= 2 and argv[0] == "-t":
-        bad = test_png_many(argv[1:])
-        for name, why in bad:
-            print("%s: %s" % (name, why))
-        print("%d image(s): %s" % (len(argv) - 1, "%d bad" % len(bad) if bad else "OK"))
-        return 1 if bad else 0
-    print("usage: python -m pure_zlib_amd.png -t A.png B.png ...", file=sys.stderr)
+        adam7 = "--adam7" in argv[1:]
+        files = [a for a in argv[1:] if a != "--adam7"]
+        if files:
+            bad = test_png_many(files, adam7=adam7)
+            for name, why in bad:
+                print("%s: %s" % (name, why))
+            print("%d image(s): %s" % (len(files), "%d bad" % len(bad) if bad else "OK"))
+            return 1 if bad else 0
+    print("usage: python -m pure_zlib_amd.png -t [--adam7] A.png B.png ...", file=sys.stderr)
     return 2
 
 

@@ -318,6 +318,30 @@ class Context:
         _ffi.check(self._L.pzg_unfilter_many(self._h, src_base, src_off, src_len, dst_base, dst_off, dst_stride, row_bytes, height, bpp,
                                              status, detail or None, n, flags), self._h)
 
+    # -- Adam7 deinterlacing (pzg_adam7_many) ----------------------------------------------------------
+    def adam7_many(self, src: np.ndarray, src_off, dst: np.ndarray, dst_off, dst_stride, width, height, pixel_bits):
+        """Thin wrapper of pzg_adam7_many on host numpy buffers: image i is its seven reduced images, unfiltered, dense and in pass
+        order at src[src_off[i]:], delivered as height[i] rows at dst[dst_off[i] + y * dst_stride[i]:].
+        Returns (status i32[n], detail u32[n,2])."""
+        arrs = [np.ascontiguousarray(a, dtype=t) for a, t in ((src_off, np.uint64), (dst_off, np.uint64), (dst_stride, np.uint64),
+                                                              (width, np.uint32), (height, np.uint32), (pixel_bits, np.uint8))]
+        n = len(arrs[0])
+        status = np.full(n, -1, dtype=np.int32)
+        detail = np.zeros((n, 2), dtype=np.uint32)
+        rc = self._L.pzg_adam7_many(self._h, src.ctypes.data, arrs[0].ctypes.data, dst.ctypes.data, arrs[1].ctypes.data, arrs[2].ctypes.data,
+                                    arrs[3].ctypes.data, arrs[4].ctypes.data, arrs[5].ctypes.data, status.ctypes.data, detail.ctypes.data, n, 0)
+        _ffi.check(rc, self._h)
+        return status, detail
+
+    def adam7_many_device(self, src_base: int, src_off: int, dst_base: int, dst_off: int, dst_stride: int, width: int, height: int,
+                          pixel_bits: int, status: int, detail: int, n: int, sync: bool = True):
+        """pzg_adam7_many on device memory, every pointer an integer address as unfilter_many_device takes them: the launch goes on
+        the context's stream behind what was enqueued before it, so src may be where unfilter_many_device(sync=False) delivers the
+        passes, and dst_base memory of the caller's own (a torch tensor's data_ptr())."""
+        flags = _ffi.DEVICE_PTRS | (0 if sync else _ffi.ASYNC)
+        _ffi.check(self._L.pzg_adam7_many(self._h, src_base, src_off, dst_base, dst_off, dst_stride, width, height, pixel_bits,
+                                          status, detail or None, n, flags), self._h)
+
     def decompress_many_sharded(self, batches, sync: bool = True, gzip: bool = False, lpt: bool = False, raw: bool = False,
                                 crc32: bool = False):
         """pzg_decompress_many_sharded: `batches` is a list of dicts (shard, n, in_base, in_off, in_len, out_base, out_off,
