@@ -92,7 +92,9 @@ extern "C" {
 #define PZG_E_SEGMENT 21  /* segments only: the blocks do not end at end_bit. d0 = 1 final block came first, 2 a block ran past; d1 = bit reached */
 #define PZG_E_FILTER 23  /* (0.5) pzg_unfilter_many only: row d0 has filter byte d1 (> 4).  d0 = 0xffffffff: the image's bpp (d1) or its
                             stride is not legal -- device arrays only, the host-pointer form refuses the call.  pzg_adam7_many: only
-                            the latter, d1 = the image's pixel_bits */
+                            the latter, d1 = the image's pixel_bits; pzg_expand_many: only the latter, d1 = color_type << 8 | bit_depth */
+#define PZG_E_PALETTE 24  /* (0.5) pzg_expand_many only: a pixel of a palette image has an index >= pal_len; d0 = its row, d1 = its x: the
+                             first such pixel in row-major order */
 #define PZG_E_SCAN 22  /* pzg_index_scan only: the chain of blocks did not reach the final block.
                           d0 = the status the chain's last segment met (0: a dead wave),
                           d1 = low 32 bits of that segment's start bit.
@@ -537,6 +539,77 @@ PZG_API int pzg_adam7_many(pzg_ctx *ctx,
         const uint8_t *src_base, const uint64_t *src_off,
         uint8_t *dst_base, const uint64_t *dst_off, const uint64_t *dst_stride,
         const uint32_t *width, const uint32_t *height, const uint8_t *pixel_bits,
+        int32_t *status, uint32_t *detail,   /* detail: 2n, or NULL */
+        uint32_t n, uint32_t flags);         /* 0, PZG_DEVICE_PTRS, PZG_DEVICE_PTRS | PZG_ASYNC */
+
+/*
+ * pzg_expand_many (0.5): EXTENSION -- pixel expansion, the last stage of a PNG decode: the rows of n images as PNG stores them
+ * (packed 1/2/4-bit samples, palette indices, big-endian 16-bit samples) written as rows of 8-bit RGBA or RGB pixels, all n in one
+ * launch, the rows of an image spread over several wavefronts.  It follows pzg_unfilter_many or pzg_adam7_many; like them it knows
+ * nothing of PNG's chunks: rows of samples in, rows of 8-bit pixels out.
+ *   desc[i]     one image (pzg_expand_desc below; its reserved words are 0):
+ *     source      row r, ceil(width * channels * bit_depth / 8) bytes, at src_base + src_off + r * src_stride.
+ *     delivery    row r, width * 4 (PZG_PIX_RGBA8: R, G, B, A) or width * 3 (PZG_PIX_RGB8: R, G, B) bytes, at
+ *                 dst_base + dst_off + r * dst_stride.  The bytes between that and the stride and everything outside the extents are
+ *                 untouched.  The dst extents overlap neither each other nor src.
+ *     type        color_type 0 (gray), 2 (RGB), 3 (palette), 4 (gray + alpha), 6 (RGBA) with bit_depth 1, 2, 4, 8, 16 for type 0,
+ *                 1, 2, 4, 8 for type 3 and 8, 16 for the others: PNG's 15 image types.
+ *     palette     type 3 only: the entries pal_off .. pal_off + pal_len - 1 (pal_len 1 .. 256) of palette_base, an array of dwords
+ *                 whose bytes in memory order are R, G, B, A.  The caller has merged PLTE and tRNS: an entry without a tRNS alpha
+ *                 has 255.  palette_base may be NULL in a call without a type 3 image.
+ *     key         has_key != 0, types 0 and 2 only (ignored for the others): the tRNS colour key, key[0] for gray and key[0..2] =
+ *                 R, G, B, at the source depth.  A pixel whose samples all equal the key gets alpha 0, every other pixel 255.  The
+ *                 comparison takes the source samples before any depth reduction: all 16 bits of a 16-bit sample.
+ *   samples     Below 8 bits pixels are packed with the leftmost in the high bits; the padding bits of a row's last byte are never
+ *               interpreted.  Gray below 8 bits is scaled by bit replication (x 255, x 85, x 17); palette indices are not scaled.
+ *               A 16-bit sample gives its HIGH BYTE (what libpng's strip_16 and OpenCV do: no rounding).  Gray fans out to
+ *               R = G = B.  The alpha of types 4 and 6 is copied, reduced the same way.  Without alpha, a key or a palette alpha,
+ *               A = 255.  PZG_PIX_RGB8 drops alpha: nothing is composited, and there is no gamma.
+ *   status[i]   PZG_OK; width or height of 0: PZG_OK, nothing read or written.
+ *               PZG_E_PALETTE  a pixel of a type 3 image has an index >= pal_len: d0 = row, d1 = x of the first such pixel in
+ *                              row-major order, whichever wavefront and lane met it.  What the image's destination extent then
+ *                              holds is unspecified; nothing outside it is written.
+ *   detail      2n words (d0, d1 per image), or NULL: 0, 0 of a PZG_OK image.
+ * flags: as for pzg_adam7_many.  0 -- every pointer is host memory: the call stages the spans of src and palette_base that the
+ * images name, desc and dst's extents through the context's arenas and returns when dst and status are filled (the rows of an image
+ * that is not PZG_OK are not copied back); PZG_DEVICE_PTRS -- every pointer is device memory, the launch goes on the context's
+ * stream (pzg_set_stream) in call order, and with PZG_ASYNC as well the call only enqueues: pzg_decompress_many, pzg_unfilter_many,
+ * [pzg_adam7_many,] pzg_expand_many and pzg_sync chain without a host round trip.  pzg_last_kernel_ms reports the launch.
+ * PZG_RC_BAD_ARG: n == 0, any other flag, a null array, a context of several devices; with host pointers also, of an image that has
+ * pixels, a (color_type, bit_depth) that is no PNG image type, an unknown out_format, a dst_stride below the delivered row, a
+ * src_stride below the source row, a pal_len of 0 or above 256 for type 3 (or a null palette_base), and a width or height of 2^31
+ * or more.  Device arrays are not read by the host: there such an image gets PZG_E_FILTER with d0 = 0xffffffff and
+ * d1 = color_type << 8 | bit_depth, and nothing of it is read or written.
+ * Offsets and strides are 64-bit.  Nothing is read but the aligned dwords that hold bytes of the image's source rows, and its palette
+ * entries [pal_off, pal_off + pal_len).
+ */
+#define PZG_PIX_RGBA8 0u
+#define PZG_PIX_RGB8  1u
+
+typedef struct pzg_expand_desc {
+    uint64_t src_off, src_stride;   /*  0,  8 */
+    uint64_t dst_off, dst_stride;   /* 16, 24 */
+    uint32_t width, height;         /* 32, 36 */
+    uint32_t pal_off;               /* 40: entry index into palette_base */
+    uint16_t pal_len;               /* 44: 1 .. 256 */
+    uint16_t key[3];                /* 46 */
+    uint8_t color_type, bit_depth;  /* 52, 53 */
+    uint8_t out_format;             /* 54: PZG_PIX_* */
+    uint8_t has_key;                /* 55 */
+    uint32_t reserved[2];           /* 56: 0 */
+} pzg_expand_desc;
+#if defined(__cplusplus)
+static_assert(sizeof(pzg_expand_desc) == 64 && offsetof(pzg_expand_desc, width) == 32 && offsetof(pzg_expand_desc, pal_off) == 40 &&
+              offsetof(pzg_expand_desc, pal_len) == 44 && offsetof(pzg_expand_desc, key) == 46 && offsetof(pzg_expand_desc, color_type) == 52 &&
+              offsetof(pzg_expand_desc, has_key) == 55 && offsetof(pzg_expand_desc, reserved) == 56, "pzg_expand_desc is 64 bytes, laid out as commented");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(pzg_expand_desc) == 64 && offsetof(pzg_expand_desc, pal_len) == 44 && offsetof(pzg_expand_desc, color_type) == 52,
+               "pzg_expand_desc is 64 bytes, laid out as commented");
+#endif
+
+PZG_API int pzg_expand_many(pzg_ctx *ctx,
+        const uint8_t *src_base, uint8_t *dst_base, const uint32_t *palette_base,
+        const pzg_expand_desc *desc,         /* n */
         int32_t *status, uint32_t *detail,   /* detail: 2n, or NULL */
         uint32_t n, uint32_t flags);         /* 0, PZG_DEVICE_PTRS, PZG_DEVICE_PTRS | PZG_ASYNC */
 

@@ -11,7 +11,8 @@ Only what the hot path needs lives here:
   indexed.py ONE large stream: an index of access points, every segment its own wavefront, reads at any offset
   gzfile.py  a gzip FILE of many members (BGZF, WARC, concatenated .gz): members found on the device, a wavefront per member
   png.py     PNG images in batches: one decode launch, one unfilter launch (pzg_unfilter_many), the pixels in one copy;
-             Adam7 images with adam7=True, deinterlaced on the device (pzg_adam7_many)
+             Adam7 images with adam7=True, deinterlaced on the device (pzg_adam7_many); expand="rgba8" | "rgb8": (H, W, 4 | 3) uint8 pixels
+             of every colour type, expanded on the device (pzg_expand_many); read_png_batch: one (N, H, W, C) tensor
   cxx/       the same module mirror in C++ (header-only)
 
 There is no CPU fallback: importing works anywhere, computing needs libpzg.so and a gfx950 device.

@@ -47,6 +47,7 @@
 #include "pzg_launch.h"
 #include "scan_core.h"  // (ScanStream, ScanResult: the tables of pzg_index_scan_many)
 #include "pzg_unfilter_kernel.h"  // (unfilter_kernel and its launcher; unfilter_core.h: its statuses, and what it takes for a legal bpp)
+#include "pzg_expand_kernel.h"    // (expand_kernel and its launcher; expand_core.h: its statuses, a legal geometry, the bytes of a row)
 #include "pzg_adam7_kernel.h"     // (adam7_kernel and its launcher; adam7_core.h: its statuses, a legal geometry, an image's source extent)
 
 namespace {
@@ -131,6 +132,7 @@ struct Shard {
     std::atomic<uint32_t> next_counter{0};
     Arena a_adler, a_scratch, a_dec;
     Arena a_gz[COUNTER_SLOTS], a_order[COUNTER_SLOTS];
+    Arena a_expand[COUNTER_SLOTS];  // pzg_expand_many: where the waves of a palette image meet (pzg_launch.h ExpandArgs::scratch)
     // ... and the kernels' token scratch (hundreds of MiB for a launch that fills the chip): STRIP_SLOTS of them, a launch
     // that takes one in use waits (on its own stream) for the launch that used it last
     // bundles (pzg_bundle_kernel.h): what the last probing launch found, fetched behind it -- a launch that decoded no stream by
@@ -489,7 +491,7 @@ void shard_destroy(Shard &sh)
     for (Arena *a : {&sh.a_adler, &sh.a_scratch, &sh.a_dec})
         if (a->p) (void)hipFree(a->p);
     for (int k = 0; k < COUNTER_SLOTS; ++k)
-        for (Arena *a : {&sh.a_gz[k], &sh.a_order[k]})
+        for (Arena *a : {&sh.a_gz[k], &sh.a_order[k], &sh.a_expand[k]})
             if (a->p) (void)hipFree(a->p);
     for (int k = 0; k < STRIP_SLOTS; ++k) {
         if (sh.a_strip[k].p) (void)hipFree(sh.a_strip[k].p);
@@ -1990,6 +1992,129 @@ int pzg_adam7_many(pzg_ctx *ctx, const uint8_t *src_base, const uint64_t *src_of
             const uint64_t rb = pzg::Adam7::bytes_of(width[i], pixel_bits[i]);
             for (uint32_t r = 0; r < height[i]; ++r) {
                 const uint64_t at = dst_off[i] + (uint64_t)r * dst_stride[i];
+                memcpy(dst_base + at, ln.h_out[0].p + (at - d_lo), rb);
+            }
+        }
+        return PZG_RC_OK;
+    });
+}
+
+// Pixel expansion (expand_core.h): the two forms of pzg_adam7_many.  The host-pointer form stages the span of src that holds the
+// images' rows, the palette entries they name, the descriptors -- their offsets counted from the spans' starts -- and the span of dst
+// that holds the extents, and copies the rows of the images that are PZG_OK -- nothing else -- from the staged span into the caller's dst.
+int pzg_expand_many(pzg_ctx *ctx, const uint8_t *src_base, uint8_t *dst_base, const uint32_t *palette_base, const pzg_expand_desc *desc, int32_t *status,
+                    uint32_t *detail, uint32_t n, uint32_t flags)
+{
+    using E = pzg::Expand;
+    static_assert(E::ST_FILTER == PZG_E_FILTER && E::ST_PALETTE == PZG_E_PALETTE && E::ST_OK == PZG_OK, "the core's statuses are the header's");
+    static_assert(E::RGBA8 == PZG_PIX_RGBA8 && E::RGB8 == PZG_PIX_RGB8, "the core's formats are the header's");
+    static_assert(sizeof(E::Desc) == sizeof(pzg_expand_desc) && offsetof(E::Desc, src_stride) == offsetof(pzg_expand_desc, src_stride) &&
+                      offsetof(E::Desc, dst_off) == offsetof(pzg_expand_desc, dst_off) && offsetof(E::Desc, dst_stride) == offsetof(pzg_expand_desc, dst_stride) &&
+                      offsetof(E::Desc, width) == offsetof(pzg_expand_desc, width) && offsetof(E::Desc, height) == offsetof(pzg_expand_desc, height) &&
+                      offsetof(E::Desc, pal_off) == offsetof(pzg_expand_desc, pal_off) && offsetof(E::Desc, pal_len) == offsetof(pzg_expand_desc, pal_len) &&
+                      offsetof(E::Desc, key) == offsetof(pzg_expand_desc, key) && offsetof(E::Desc, color_type) == offsetof(pzg_expand_desc, color_type) &&
+                      offsetof(E::Desc, bit_depth) == offsetof(pzg_expand_desc, bit_depth) && offsetof(E::Desc, out_format) == offsetof(pzg_expand_desc, out_format) &&
+                      offsetof(E::Desc, has_key) == offsetof(pzg_expand_desc, has_key),
+                  "the core's descriptor is the header's");
+    if (!ctx_live(ctx) || n == 0) return PZG_RC_BAD_ARG;
+    if ((flags & ~(PZG_DEVICE_PTRS | PZG_ASYNC)) || ((flags & PZG_ASYNC) && !(flags & PZG_DEVICE_PTRS))) return PZG_RC_BAD_ARG;
+    if (ctx->shards.size() != 1) return PZG_RC_BAD_ARG;
+    if (!src_base || !dst_base || !desc || !status) return PZG_RC_BAD_ARG;
+    Shard &sh = *ctx->shards[0];
+    if (flags & PZG_DEVICE_PTRS)
+        return guarded(ctx, "pzg_expand_many", [&]() -> int {
+            std::lock_guard<std::mutex> g(sh.mu);
+            HIP_TRY(ctx, hipSetDevice(sh.device));
+            // (its own scratch: launches on different streams may overlap; arena_reserve frees a slot's old one through hipFree only)
+            Arena &scr = sh.a_expand[sh.next_counter.fetch_add(1u) % COUNTER_SLOTS];
+            const int rc = arena_reserve(ctx, scr, pzg::expand_scratch_bytes(n));
+            if (rc != PZG_RC_OK) return rc;
+            pzg::ExpandArgs a{src_base, dst_base, palette_base, desc, (uint64_t *)scr.p, status, detail, n};
+            HIP_TRY(ctx, hipMemsetAsync(scr.p, 0, pzg::expand_scratch_bytes(n), sh.stream));
+            HIP_TRY(ctx, hipEventRecord(sh.ev0, sh.stream));
+            HIP_TRY(ctx, pzg::launch_expand(a, sh.stream));
+            HIP_TRY(ctx, hipEventRecord(sh.ev1, sh.stream));
+            sh.timed = true;
+            sh.last_was_host = false;
+            if (!(flags & PZG_ASYNC)) HIP_TRY(ctx, hipStreamSynchronize(sh.stream));
+            return PZG_RC_OK;
+        });
+    // host pointers: the spans, and what the device form leaves to the kernel
+    const E::Desc *hd = (const E::Desc *)(const void *)desc;
+    uint64_t s_lo = ~0ull, s_hi = 0, d_lo = ~0ull, d_hi = 0, p_lo = ~0ull, p_hi = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const E::Desc &D = hd[i];
+        if (D.width == 0u || D.height == 0u) continue;
+        if (!E::geometry_ok(D) || (D.color_type == 3u && !palette_base)) return PZG_RC_BAD_ARG;
+        const uint64_t rows = D.height - 1u;
+        d_lo = std::min(d_lo, D.dst_off);
+        d_hi = std::max(d_hi, D.dst_off + rows * D.dst_stride + E::dst_row_bytes(D.width, D.out_format));
+        s_lo = std::min(s_lo, D.src_off);
+        s_hi = std::max(s_hi, D.src_off + rows * D.src_stride + E::src_row_bytes(D.width, D.color_type, D.bit_depth));
+        if (D.color_type == 3u) {
+            p_lo = std::min(p_lo, (uint64_t)D.pal_off);
+            p_hi = std::max(p_hi, (uint64_t)D.pal_off + D.pal_len);
+        }
+    }
+    if (d_lo > d_hi) {  // nothing but empty images
+        for (uint32_t i = 0; i < n; ++i) status[i] = PZG_OK;
+        if (detail) memset(detail, 0, 8 * (size_t)n);
+        return PZG_RC_OK;
+    }
+    if (p_lo > p_hi) p_lo = p_hi = 0;
+    return guarded(ctx, "pzg_expand_many", [&]() -> int {
+        LaneCall call(ctx, sh);
+        if (call.rc != PZG_RC_OK) return call.rc;
+        Lane &ln = call.ln;
+        hipStream_t st = call.st;
+        int rc;
+        // the spans keep their places modulo 16: a row is fetched and stored at the alignment the caller gave it
+        const size_t s_skew = (size_t)((uintptr_t)(src_base + s_lo) & 15u), d_skew = (size_t)((uintptr_t)(dst_base + d_lo) & 15u);
+        const size_t s_bytes = (size_t)(s_hi - s_lo), d_bytes = (size_t)(d_hi - d_lo);
+        const size_t m_desc = pad256(sizeof(E::Desc) * (size_t)n), m_pal = pad256(4 * (size_t)(p_hi - p_lo)), m_scr = pad256(pzg::expand_scratch_bytes(n));
+        const size_t row4 = pad256(4 * (size_t)n), m_in = m_desc + m_pal + m_scr, m_all = m_in + row4 + pad256(8 * (size_t)n);
+        if ((rc = arena_reserve(ctx, ln.d_in[0], s_bytes + 64)) != PZG_RC_OK) return rc;
+        if ((rc = arena_reserve(ctx, ln.d_out[0], d_bytes + 64)) != PZG_RC_OK) return rc;
+        if ((rc = arena_reserve(ctx, ln.d_meta[0], m_all)) != PZG_RC_OK) return rc;
+        if ((rc = pinned_reserve(ctx, ln.h_meta[0], m_all)) != PZG_RC_OK) return rc;
+        if ((rc = pinned_reserve(ctx, ln.h_out[0], d_bytes + 64)) != PZG_RC_OK) return rc;
+        uint8_t *hm = ln.h_meta[0].p, *dm = (uint8_t *)ln.d_meta[0].p;
+        E::Desc *sd = (E::Desc *)(void *)hm;
+        for (uint32_t i = 0; i < n; ++i) {
+            sd[i] = hd[i];
+            const bool empty = hd[i].width == 0u || hd[i].height == 0u;
+            sd[i].src_off = empty ? 0u : hd[i].src_off - s_lo;
+            sd[i].dst_off = empty ? 0u : hd[i].dst_off - d_lo;
+            sd[i].pal_off = empty || hd[i].color_type != 3u ? 0u : (uint32_t)(hd[i].pal_off - p_lo);
+        }
+        if (p_hi > p_lo) memcpy(hm + m_desc, palette_base + p_lo, 4 * (size_t)(p_hi - p_lo));
+        memset(hm + m_desc + m_pal, 0, m_scr);  // (the scratch goes up zeroed with the rest)
+        HIP_TRY(ctx, hipMemcpyAsync(dm, hm, m_in, hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemcpyAsync((uint8_t *)ln.d_in[0].p + s_skew, src_base + s_lo, s_bytes, hipMemcpyHostToDevice, st));
+        pzg::ExpandArgs a{};
+        a.src_base = (const uint8_t *)ln.d_in[0].p + s_skew;
+        a.dst_base = (uint8_t *)ln.d_out[0].p + d_skew;
+        a.palette_base = (const uint32_t *)(void *)(dm + m_desc);
+        a.desc = dm;
+        a.scratch = (uint64_t *)(void *)(dm + m_desc + m_pal);
+        a.status = (int32_t *)(void *)(dm + m_in);
+        a.detail = (uint32_t *)(void *)(dm + m_in + row4);
+        a.n = n;
+        HIP_TRY(ctx, call.begin_timed());
+        HIP_TRY(ctx, pzg::launch_expand(a, st));
+        HIP_TRY(ctx, call.end_timed());
+        HIP_TRY(ctx, hipMemcpyAsync(hm + m_in, dm + m_in, m_all - m_in, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipMemcpyAsync(ln.h_out[0].p, a.dst_base, d_bytes, hipMemcpyDeviceToHost, st));
+        if ((rc = call.finish()) != PZG_RC_OK) return rc;
+        const int32_t *h_status = (const int32_t *)(const void *)(hm + m_in);
+        memcpy(status, h_status, 4 * (size_t)n);
+        if (detail) memcpy(detail, hm + m_in + row4, 8 * (size_t)n);
+        for (uint32_t i = 0; i < n; ++i) {  // the rows the kernel delivered
+            const E::Desc &D = hd[i];
+            if (D.width == 0u || D.height == 0u || h_status[i] != PZG_OK) continue;
+            const uint64_t rb = E::dst_row_bytes(D.width, D.out_format);
+            for (uint32_t r = 0; r < D.height; ++r) {
+                const uint64_t at = D.dst_off + (uint64_t)r * D.dst_stride;
                 memcpy(dst_base + at, ln.h_out[0].p + (at - d_lo), rb);
             }
         }

@@ -201,6 +201,9 @@ extern "C" int pzg_error_message(const uint8_t *in, uint64_t in_len, int32_t sta
         if (d0 == 0xffffffffu) snprintf(buf, buf_len, "Block format error: filter unit of %u bytes, or a stride below the row", d1);
         else snprintf(buf, buf_len, "Block format error: row %u has filter type %u", d0, d1);
         break;
+    case PZG_E_PALETTE:  // extension (pzg_expand_many)
+        snprintf(buf, buf_len, "Block format error: row %u, pixel %u: palette index outside the palette", d0, d1);
+        break;
     default: snprintf(buf, buf_len, "unknown status %d", status); break;
     }
     return (int)strlen(buf);

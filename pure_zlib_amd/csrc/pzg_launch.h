@@ -208,6 +208,21 @@ struct Adam7Args {
     uint32_t n;
 };
 
+// pixel expansion (pzg_expand_kernel.h, expand_core.h; compiled with pzg_api.cpp): the rows of an image over the grid's y.  Every pointer
+// is device memory.  desc: n descriptors of 64 bytes, pzg_expand_desc as the core sees it (Expand::Desc); scratch: two zeroed 64-bit
+// words per image (expand_scratch_bytes), where the waves of a palette image meet.
+struct ExpandArgs {
+    const uint8_t *src_base;
+    uint8_t *dst_base;
+    const uint32_t *palette_base;  // may be null where no image has a palette
+    const void *desc;              // n
+    uint64_t *scratch;             // 2n, zero
+    int32_t *status;               // n
+    uint32_t *detail;              // 2n or null
+    uint32_t n;
+};
+inline size_t expand_scratch_bytes(uint32_t n) { return 16 * (size_t)n; }
+
 // partials: 3 * 4 * ceil(max_waves / 4) uint32 of device scratch
 hipError_t launch_adler32(const uint8_t *buf, uint64_t len, uint32_t init, uint32_t *partials, uint32_t max_waves,
                           uint32_t *out, hipStream_t stream);

@@ -8,11 +8,18 @@ checks their CRC-32s with the system's zlib; nothing is inflated on the CPU.  De
 
     read_png_many(blobs_or_paths)  -> [PngImage, or the DecompressionError / ValueError / NotImplementedError of that image]
     read_png(blob_or_path)         -> PngImage                  (raises)
+    read_png_batch(blobs_or_paths) -> (one (N, H, W, C) uint8 torch tensor on the device, [(index, exception)])
     test_png_many(blobs_or_paths)  -> [(index_or_name, problem)]   (empty: every image is sound)
     python -m pure_zlib_amd.png -t [--adam7] A.png B.png ...
 
-Colour types 0, 2, 3, 4 and 6 at their legal bit depths.  `data` is the samples as the file stores them -- no palette expansion, no
-bit-depth expansion, no gamma, no alpha handling: a viewer's work.
+Colour types 0, 2, 3, 4 and 6 at their legal bit depths.  Without `expand`, `data` is the samples as the file stores them: packed
+rows below 8 bits, palette indices, big-endian 16-bit samples, tRNS as raw bytes.  With expand="rgba8" or "rgb8" one more launch,
+pzg_expand_many, behind the others on the same stream turns them into (H, W, 4 | 3) uint8 pixels on the device, whatever the file's
+type: the palette is looked up (tRNS as its alpha), gray below 8 bits is scaled by bit replication, a 16-bit sample gives its high
+byte, gray fans out to R = G = B, a tRNS colour key makes its pixels transparent (compared at the file's depth), and "rgb8" drops
+alpha.  The unfilter and Adam7 launches then deliver into a device scratch in the file's format, and the expansion writes the pixel
+buffer (or device_out, whose offsets and strides then describe the EXPANDED rows).  Still one sync and one copy out.  Not done:
+16-bit or gray output, compositing over a background, gamma, sBIT.  expand=None issues exactly the launches it always did.
 
 Adam7-interlaced images are read with adam7=True (--adam7); without it such an image is NotImplementedError, for that image only,
 and nothing else changes.  An interlaced image's stream is its seven reduced images, each filtered on its own, so its exact decoded
@@ -32,7 +39,7 @@ from typing import List, Optional, Sequence, Tuple, Union
 import numpy as np
 
 from . import _ffi
-from .zlib import Context, DecompressionError, PinnedArena, default_context, error_from_status
+from .zlib import EXPAND_DESC, Context, DecompressionError, PinnedArena, default_context, error_from_status
 
 SIGNATURE = b"\x89PNG\r\n\x1a\n"
 _CHANNELS = {0: 1, 2: 3, 3: 1, 4: 2, 6: 4}
@@ -48,6 +55,7 @@ class PngImage:
     palette: Optional[bytes]  # PLTE as it stands (3 bytes an entry), or None
     trns: Optional[bytes]     # tRNS as it stands, or None
     data: Optional[np.ndarray]  # (H, W, C) uint8 | (H, W, C) >u2 | (H, row_bytes) packed uint8 below 8 bits; None with device_out
+    expanded: Optional[str] = None  # "rgba8" | "rgb8": data (or device_out) holds (H, W, 4 | 3) uint8 pixels; None: the file's samples
 
     @property
     def channels(self) -> int:
@@ -80,9 +88,26 @@ def _passes(img: PngImage) -> List[Tuple[int, int, int]]:
     return out
 
 
-def _parse(name: str, blob: bytes, adam7: bool = False) -> Tuple[PngImage, bytes, bool]:
+_EXPAND = {"rgba8": (_ffi.PIX_RGBA8, 4), "rgb8": (_ffi.PIX_RGB8, 3)}  # expand -> (out_format, bytes of a pixel)
+
+
+def _check_trns(name: str, img: PngImage) -> None:
+    """What the expansion needs of tRNS (PNG specification 11.3.2): a key of one or three 16-bit values, or at most one alpha per
+    palette entry; none where the image has an alpha channel."""
+    if img.trns is None:
+        return
+    if img.color_type in (4, 6):
+        raise ValueError("%s: tRNS in an image of colour type %d, which has an alpha channel" % (name, img.color_type))
+    if img.color_type == 3:
+        if not 1 <= len(img.trns) <= len(img.palette) // 3:
+            raise ValueError("%s: tRNS of %d entries for a palette of %d" % (name, len(img.trns), len(img.palette) // 3))
+    elif len(img.trns) != 2 * img.channels:
+        raise ValueError("%s: tRNS of %d bytes in an image of colour type %d" % (name, len(img.trns), img.color_type))
+
+
+def _parse(name: str, blob: bytes, adam7: bool = False, expand: bool = False) -> Tuple[PngImage, bytes, bool]:
     """(the image without its data, its IDAT payloads joined, whether it is interlaced); raises ValueError / NotImplementedError
-    naming the image."""
+    naming the image.  expand: tRNS is held to its colour type as well (without it, it is passed on as it stands)."""
     if blob[:8] != SIGNATURE:
         raise ValueError("%s: not a PNG file (bad signature)" % name)
     at, img, idat, seen_idat, idat_closed, palette, trns, laced = 8, None, [], False, False, None, None, False
@@ -136,6 +161,8 @@ def _parse(name: str, blob: bytes, adam7: bool = False) -> Tuple[PngImage, bytes
     if img.color_type == 3 and palette is None:
         raise ValueError("%s: a palette image without PLTE" % name)
     img.palette, img.trns = palette, trns
+    if expand:
+        _check_trns(name, img)
     return img, b"".join(idat), laced
 
 
@@ -155,12 +182,17 @@ def _load(src) -> Tuple[Optional[str], bytes]:
 
 
 def read_png_many(blobs_or_paths: Sequence[Union[str, os.PathLike, bytes, bytearray, memoryview]], ctx: Optional[Context] = None,
-                  device_out: Optional[Tuple[int, Sequence[int], Sequence[int]]] = None, adam7: bool = False) -> List[Union[PngImage, Exception]]:
+                  device_out: Optional[Tuple[int, Sequence[int], Sequence[int]]] = None, adam7: bool = False,
+                  expand: Optional[str] = None) -> List[Union[PngImage, Exception]]:
     """Every image of the batch, or in its place the exception that read_png would raise for it: a bad image never disturbs its
     neighbours.  device_out = (ptr, offsets, strides): the rows of image i land at ptr + offsets[i] + r * strides[i] in device
     memory of the caller's (a torch tensor's data_ptr()), nothing is copied out and `data` is None.  adam7: Adam7-interlaced
-    images are read too, deinterlaced on the device (without it each is NotImplementedError)."""
+    images are read too, deinterlaced on the device (without it each is NotImplementedError).  expand = "rgba8" | "rgb8": `data` is
+    (H, W, 4 | 3) uint8 pixels for every colour type, expanded on the device (the module's docstring has the rules), and device_out's
+    offsets and strides describe those rows; an image with an error may leave anything in its own rows there."""
     import torch
+    if expand is not None and expand not in _EXPAND:
+        raise ValueError("expand: None, 'rgba8' or 'rgb8', not %r" % (expand,))
     results: List[Union[PngImage, Exception, None]] = [None] * len(blobs_or_paths)
     names, good, laced = [], [], []  # good: (index, image, stream); laced: the interlaced ones, as (place in good, its passes)
     for k, src in enumerate(blobs_or_paths):
@@ -168,7 +200,7 @@ def read_png_many(blobs_or_paths: Sequence[Union[str, os.PathLike, bytes, bytear
         try:
             path, blob = _load(src)
             name = path or name
-            img, z, lace = _parse(name, blob, adam7)
+            img, z, lace = _parse(name, blob, adam7, expand is not None)
             if lace:
                 laced.append((len(good), _passes(img)))
             good.append((k, img, z))
@@ -192,12 +224,23 @@ def read_png_many(blobs_or_paths: Sequence[Union[str, os.PathLike, bytes, bytear
     dec_off[1:] = np.cumsum(pad(dec_cap + np.uint64(4)))[:-1]  # (4: a stream that decodes to MORE than its capacity claims no neighbour's dword)
     pix_off[1:] = np.cumsum(pad(pix))[:-1]
     stride = row_bytes.astype(np.uint64)
+    if expand is not None:
+        # the unfilter and Adam7 launches deliver the file's rows dense into a scratch (file_off, file_stride); pix, pix_off and
+        # stride become those of the expanded rows, which the expansion writes
+        file_off, file_stride, tot_file = pix_off, stride, int(pix_off[-1] + pad(pix)[-1]) + 16
+        out_rb = np.array([i.width * _EXPAND[expand][1] for _k, i, _z in good], dtype=np.uint64)
+        pix = height.astype(np.uint64) * out_rb
+        pix_off = np.zeros(n, dtype=np.uint64)
+        pix_off[1:] = np.cumsum(pad(pix))[:-1]
+        stride = out_rb
     if device_out is not None:
         out_ptr = int(device_out[0])
         pix_off = np.array([device_out[1][k] for k, _i, _z in good], dtype=np.uint64)
         stride = np.array([device_out[2][k] for k, _i, _z in good], dtype=np.uint64)
-        if (stride < row_bytes).any():
+        if (stride < (row_bytes if expand is None else out_rb)).any():
             raise ValueError("device_out: a stride below the image's row_bytes")
+    if expand is None:
+        file_off, file_stride = pix_off, stride
     tot_in = int(in_off[-1] + pad(in_len)[-1]) + 16
     tot_dec = int(dec_off[-1] + pad(dec_cap + np.uint64(4))[-1]) + 16
     tot_pix = int(pix_off[-1] + pad(pix)[-1]) + 16
@@ -212,7 +255,7 @@ def read_png_many(blobs_or_paths: Sequence[Union[str, os.PathLike, bytes, bytear
         plain_height = height.copy()
         for j, _ps in laced:
             plain_height[j] = 0  # (no rows: the first unfilter launch neither reads nor writes an interlaced image)
-        d_meta = [up(a) for a in (in_off, in_len, dec_off, dec_cap, pix_off, stride, row_bytes, plain_height, bpp)]
+        d_meta = [up(a) for a in (in_off, in_len, dec_off, dec_cap, file_off, file_stride, row_bytes, plain_height, bpp)]
         d_dec = torch.empty(tot_dec, dtype=torch.uint8, device=dev)
         d_pix = torch.empty(tot_pix, dtype=torch.uint8, device=dev) if device_out is None else None
         d_out_len = torch.zeros(8 * n, dtype=torch.uint8, device=dev)
@@ -233,27 +276,47 @@ def read_png_many(blobs_or_paths: Sequence[Union[str, os.PathLike, bytes, bytear
             m, jj = len(jobs), [j for j, _ps in laced]
             col = lambda c, t: np.array([job[c] for job in jobs], dtype=t)  # noqa: E731
             d_jobs = [up(a) for a in (col(0, np.uint64), col(1, np.uint64), col(2, np.uint64), col(3, np.uint64), col(3, np.uint32), col(4, np.uint32),
-                                      col(5, np.uint8), np.array(scr_off, dtype=np.uint64), pix_off[jj], stride[jj],
+                                      col(5, np.uint8), np.array(scr_off, dtype=np.uint64), file_off[jj], file_stride[jj],
                                       np.array([good[j][1].width for j in jj], dtype=np.uint32), height[jj],
                                       np.array([good[j][1].channels * good[j][1].bit_depth for j in jj], dtype=np.uint8))]
             d_scr = torch.empty(scr_at + 16, dtype=torch.uint8, device=dev)
             d_jstatus = torch.zeros(4 * m, dtype=torch.uint8, device=dev)   # the pass jobs'
             d_jdetail = torch.zeros(8 * m, dtype=torch.uint8, device=dev)
             d_astatus = torch.zeros(4 * len(jj), dtype=torch.uint8, device=dev)  # the deinterlacing's
+        if expand is not None:
+            desc, pal = _expand_descriptors([i for _k, i, _z in good], file_off, file_stride, pix_off, stride, _EXPAND[expand][0])
+            d_file = torch.empty(tot_file, dtype=torch.uint8, device=dev)
+            d_desc, d_pal = up(desc), up(pal)
+            d_xstatus = torch.zeros(4 * n, dtype=torch.uint8, device=dev)  # the expansion's
+            d_xdetail = torch.zeros(8 * n, dtype=torch.uint8, device=dev)
         torch.cuda.synchronize(dev)
         p = [t.data_ptr() for t in d_meta]
         ctx.decompress_many_device(d_in.data_ptr(), p[0], p[1], d_dec.data_ptr(), p[2], p[3], d_out_len.data_ptr(), d_status.data_ptr(),
                                    d_detail.data_ptr(), 0, 0, n, sync=False)
         pix_ptr = out_ptr if device_out is not None else d_pix.data_ptr()
+        file_ptr = pix_ptr if expand is None else d_file.data_ptr()
         if len(laced) < n:  # (a batch of interlaced images only has nothing for this launch)
-            ctx.unfilter_many_device(d_dec.data_ptr(), p[2], d_out_len.data_ptr(), pix_ptr, p[4], p[5], p[6], p[7], p[8], d_status.data_ptr() + 4 * n,
+            ctx.unfilter_many_device(d_dec.data_ptr(), p[2], d_out_len.data_ptr(), file_ptr, p[4], p[5], p[6], p[7], p[8], d_status.data_ptr() + 4 * n,
                                      d_detail.data_ptr() + 8 * n, n, sync=False)
         if laced:
             q = [t.data_ptr() for t in d_jobs]
             ctx.unfilter_many_device(d_dec.data_ptr(), q[0], q[1], d_scr.data_ptr(), q[2], q[3], q[4], q[5], q[6], d_jstatus.data_ptr(),
                                      d_jdetail.data_ptr(), m, sync=False)
-            ctx.adam7_many_device(d_scr.data_ptr(), q[7], pix_ptr, q[8], q[9], q[10], q[11], q[12], d_astatus.data_ptr(), 0, len(jj), sync=False)
+            ctx.adam7_many_device(d_scr.data_ptr(), q[7], file_ptr, q[8], q[9], q[10], q[11], q[12], d_astatus.data_ptr(), 0, len(jj), sync=False)
+        if expand is not None:
+            ctx.expand_many_device(d_file.data_ptr(), pix_ptr, d_pal.data_ptr(), d_desc.data_ptr(), d_xstatus.data_ptr(), d_xdetail.data_ptr(), n,
+                                   sync=False)
         ctx.sync()
+        bad_index = {}  # place in good -> (row, x, the index found there) of an image the expansion refused
+        if expand is not None:
+            xstatus, xdetail = d_xstatus.cpu().numpy().view(np.int32), d_xdetail.cpu().numpy().view(np.uint32).reshape(n, 2)
+            for j in np.flatnonzero(xstatus != _ffi.OK):
+                row, x, depth = int(xdetail[j, 0]), int(xdetail[j, 1]), good[j][1].bit_depth
+                if int(xstatus[j]) != _ffi.E_PALETTE:
+                    bad_index[int(j)] = None
+                    continue
+                byte = int(d_file[int(file_off[j]) + row * int(file_stride[j]) + x * depth // 8])  # (one byte back: the index itself)
+                bad_index[int(j)] = (row, x, (byte >> (8 - depth - x * depth % 8)) & ((1 << depth) - 1))
         pass_error = {}  # place in good -> what its passes and its deinterlacing say, the first pass in pass order first
         if laced:
             jstatus, jdetail = d_jstatus.cpu().numpy().view(np.int32), d_jdetail.cpu().numpy().view(np.uint32).reshape(m, 2)
@@ -292,20 +355,89 @@ def read_png_many(blobs_or_paths: Sequence[Union[str, os.PathLike, bytes, bytear
                                             ust, (int(detail[1, j, 0]), int(detail[1, j, 1])))
         elif ust != _ffi.OK:
             results[k] = _format_error("%s: not enough image data" % name)
+        elif j in bad_index:
+            if bad_index[j] is None:
+                results[k] = _format_error("%s: the image's pixels could not be expanded" % name)
+            else:
+                row, x, index = bad_index[j]
+                results[k] = DecompressionError("FormatError", "%s: row %d, pixel %d: palette index %d of %d" % (name, row, x, index, len(img.palette) // 3),
+                                                _ffi.E_PALETTE, (row, x))
         else:
             if pixels is not None:
                 o = int(pix_off[j])
-                img.data = _shape(img, pixels[o:o + int(pix[j])].copy())
+                flat = pixels[o:o + int(pix[j])].copy()
+                img.data = _shape(img, flat) if expand is None else flat.reshape(img.height, img.width, _EXPAND[expand][1])
+            img.expanded = expand
             results[k] = img
     return results
 
 
-def read_png(blob_or_path, ctx: Optional[Context] = None, adam7: bool = False) -> PngImage:
+def _expand_descriptors(images: Sequence[PngImage], src_off, src_stride, dst_off, dst_stride, out_format: int) -> Tuple[np.ndarray, np.ndarray]:
+    """(the pzg_expand_desc of every image, the palettes one behind the other as R, G, B, A entries -- PLTE with tRNS as its alpha,
+    255 where tRNS has none)."""
+    desc = np.zeros(len(images), dtype=EXPAND_DESC)
+    desc["src_off"], desc["src_stride"], desc["dst_off"], desc["dst_stride"] = src_off, src_stride, dst_off, dst_stride
+    desc["out_format"] = out_format
+    pals, at = [], 0
+    for d, img in zip(desc, images):
+        d["width"], d["height"], d["color_type"], d["bit_depth"] = img.width, img.height, img.color_type, img.bit_depth
+        if img.color_type == 3:
+            entries = np.full((len(img.palette) // 3, 4), 255, dtype=np.uint8)
+            entries[:, :3] = np.frombuffer(img.palette, dtype=np.uint8).reshape(-1, 3)
+            if img.trns is not None:
+                entries[:len(img.trns), 3] = np.frombuffer(img.trns, dtype=np.uint8)
+            d["pal_off"], d["pal_len"] = at, len(entries)
+            pals.append(entries)
+            at += len(entries)
+        elif img.trns is not None:
+            d["has_key"] = 1
+            d["key"][:img.channels] = struct.unpack(">%dH" % img.channels, img.trns)
+    pals.append(np.zeros((1, 4), dtype=np.uint8))  # (never empty)
+    return desc, np.concatenate(pals).view("<u4").reshape(-1)
+
+
+def read_png(blob_or_path, ctx: Optional[Context] = None, adam7: bool = False, expand: Optional[str] = None) -> PngImage:
     """One image.  Raises what read_png_many would put in its place."""
-    r = read_png_many([blob_or_path], ctx, adam7=adam7)[0]
+    r = read_png_many([blob_or_path], ctx, adam7=adam7, expand=expand)[0]
     if isinstance(r, Exception):
         raise r
     return r
+
+
+def read_png_batch(blobs_or_paths, expand: str = "rgb8", adam7: bool = False, ctx: Optional[Context] = None):
+    """Images that all share one size as ONE (N, H, W, C) uint8 torch tensor on the context's device, C = 4 ("rgba8") or 3 ("rgb8"):
+    read_png_many(..., expand=expand) delivering straight into it.  H and W are those of the first image whose IHDR can be read.
+    Returns (tensor, errors), errors = [(index, exception)]: an image of another size or with an error of its own is listed there,
+    and its slab of the tensor is zero."""
+    import torch
+    ctx = ctx or default_context()
+    channels, n = _EXPAND[expand][1], len(blobs_or_paths)
+    blobs, sizes, errors = [], [], {}
+    for k, src in enumerate(blobs_or_paths):
+        try:
+            blobs.append(_load(src)[1])
+        except OSError as e:
+            blobs.append(b"")
+            errors[k] = e
+        b = blobs[-1]
+        sizes.append(struct.unpack_from(">II", b, 16) if b[:8] == SIGNATURE and b[12:16] == b"IHDR" and len(b) >= 24 else None)
+    size = next((s for s in sizes if s is not None and 0 < s[0] < 1 << 31 and 0 < s[1] < 1 << 31), None)
+    if size is None:
+        raise ValueError("read_png_batch: no image of the batch has a readable IHDR")
+    w, h = size
+    out = torch.zeros((n, h, w, channels), dtype=torch.uint8, device=torch.device("cuda", ctx.device))
+    mine = [k for k in range(n) if k not in errors and sizes[k] in (size, None)]  # (None: read_png_many says what is wrong with it)
+    for k in range(n):
+        if k not in errors and k not in mine:
+            errors[k] = ValueError("#%d: an image of %d x %d in a batch of %d x %d" % (k, sizes[k][0], sizes[k][1], w, h))
+    slab = h * w * channels
+    got = read_png_many([blobs[k] for k in mine], ctx, device_out=(out.data_ptr(), {j: k * slab for j, k in enumerate(mine)},
+                                                                   {j: w * channels for j in range(len(mine))}), adam7=adam7, expand=expand)
+    for k, r in zip(mine, got):
+        if isinstance(r, Exception):
+            errors[k] = r
+            out[k].zero_()
+    return out, sorted(errors.items())
 
 
 def test_png_many(blobs_or_paths, ctx: Optional[Context] = None, adam7: bool = False) -> List[Tuple[Union[int, str], str]]:

@@ -98,6 +98,12 @@ class Right:
 Either = Union[Left, Right]
 LazyByteString = Union[bytes, bytearray, memoryview, Sequence[bytes]]
 
+# pzg_expand_desc (include/pzg.h) as a numpy record: one image of Context.expand_many
+EXPAND_DESC = np.dtype([("src_off", "<u8"), ("src_stride", "<u8"), ("dst_off", "<u8"), ("dst_stride", "<u8"), ("width", "<u4"), ("height", "<u4"),
+                        ("pal_off", "<u4"), ("pal_len", "<u2"), ("key", "<u2", (3,)), ("color_type", "u1"), ("bit_depth", "u1"), ("out_format", "u1"),
+                        ("has_key", "u1"), ("reserved", "<u4", (2,))])
+assert EXPAND_DESC.itemsize == 64
+
 _STATUS_CONSTRUCTOR = {
     _ffi.E_TRUNCATED: "DecompressionError",
     _ffi.E_HDR_FCHECK: "HeaderError",
@@ -117,6 +123,7 @@ _STATUS_CONSTRUCTOR = {
     _ffi.E_GZIP_ISIZE: "ChecksumError",
     _ffi.E_DICT: "HeaderError",         # extension (preset dictionaries)
     _ffi.E_FILTER: "FormatError",       # extension (pzg_unfilter_many)
+    _ffi.E_PALETTE: "FormatError",      # extension (pzg_expand_many)
 }
 
 
@@ -341,6 +348,30 @@ class Context:
         flags = _ffi.DEVICE_PTRS | (0 if sync else _ffi.ASYNC)
         _ffi.check(self._L.pzg_adam7_many(self._h, src_base, src_off, dst_base, dst_off, dst_stride, width, height, pixel_bits,
                                           status, detail or None, n, flags), self._h)
+
+    # -- pixel expansion (pzg_expand_many) -----------------------------------------------------------------
+    def expand_many(self, src: np.ndarray, dst: np.ndarray, palette: Optional[np.ndarray], desc: np.ndarray):
+        """Thin wrapper of pzg_expand_many on host numpy buffers: image i is described by desc[i] (EXPAND_DESC: a structured array of
+        pzg_expand_desc), its rows as PNG stores them in src, its RGBA8 / RGB8 rows delivered into dst; palette: uint32 entries whose
+        bytes in memory order are R, G, B, A (None: no palette image).  Returns (status i32[n], detail u32[n,2])."""
+        desc = np.ascontiguousarray(desc)
+        if desc.dtype.itemsize != EXPAND_DESC.itemsize:
+            raise ValueError("desc: records of %d bytes (EXPAND_DESC)" % EXPAND_DESC.itemsize)
+        n = len(desc)
+        status = np.full(n, -1, dtype=np.int32)
+        detail = np.zeros((n, 2), dtype=np.uint32)
+        pal = None if palette is None else np.ascontiguousarray(palette, dtype=np.uint32)
+        rc = self._L.pzg_expand_many(self._h, src.ctypes.data, dst.ctypes.data, pal.ctypes.data if pal is not None else None, desc.ctypes.data,
+                                     status.ctypes.data, detail.ctypes.data, n, 0)
+        _ffi.check(rc, self._h)
+        return status, detail
+
+    def expand_many_device(self, src_base: int, dst_base: int, palette_base: int, desc: int, status: int, detail: int, n: int, sync: bool = True):
+        """pzg_expand_many on device memory, every pointer an integer address as adam7_many_device takes them: the launch goes on the
+        context's stream behind what was enqueued before it, so src may be where unfilter_many_device(sync=False) or
+        adam7_many_device(sync=False) deliver, and dst_base memory of the caller's own (a torch tensor's data_ptr())."""
+        flags = _ffi.DEVICE_PTRS | (0 if sync else _ffi.ASYNC)
+        _ffi.check(self._L.pzg_expand_many(self._h, src_base, dst_base, palette_base or None, desc, status, detail or None, n, flags), self._h)
 
     def decompress_many_sharded(self, batches, sync: bool = True, gzip: bool = False, lpt: bool = False, raw: bool = False,
                                 crc32: bool = False):
