@@ -19,7 +19,7 @@
 //   a call's pieces   LaneCall (a synchronous call on lane 0: lock, prepare, kernel span, drained if it leaves early), CallScratch,
 //                     stage_input, copy_back_windows; MetaBlock (the packed per-stream arrays) and the two inflate_args();
 //                     extents_ok / dict_extents_ok
-//   paths             launch_device (device pointers), host_path (pipelined ranges), dict_path (dictionaries, segments)
+//   paths             launch_device (device pointers), host_path (pipelined ranges), dict_path (dictionaries, segments), stream_launch, image_stage_host
 //   entry points      init and options, decompress_many*, the index calls, the gzip member calls, the sharded call,
 //                     resumable decoders, Adler-32, timing and texts
 #include <hip/hip_runtime.h>
@@ -45,6 +45,7 @@
 #include "../../include/pzg.h"
 #include "pzg_helpers.h"
 #include "pzg_launch.h"
+#include "pzg_stage_span.h"  // (the image stages' host-pointer arithmetic, and pad256)
 #include "scan_core.h"  // (ScanStream, ScanResult: the tables of pzg_index_scan_many)
 #include "pzg_unfilter_kernel.h"  // (unfilter_kernel and its launcher; unfilter_core.h: its statuses, and what it takes for a legal bpp)
 #include "pzg_expand_kernel.h"    // (expand_kernel and its launcher; expand_core.h: its statuses, a legal geometry, the bytes of a row)
@@ -644,7 +645,7 @@ struct Range {
 };
 
 inline size_t pad16(size_t x) { return (x + 15u) & ~(size_t)15u; }
-inline size_t pad256(size_t x) { return (x + 255u) & ~(size_t)255u; }
+using pzg::pad256;
 
 // The launch arguments of n streams whose arrays are the caller's own (device pointers), with the optional dictionary and segment arrays.
 pzg::InflateArgs inflate_args(const HostBatch &b, uint32_t n, const uint8_t *dict_base = nullptr, const uint64_t *dict_off = nullptr,
@@ -1133,6 +1134,94 @@ void lpt_order(const uint64_t *out_cap, std::vector<uint32_t> &idx)
     bool uniform = true;
     for (size_t k = 1; k < idx.size() && uniform; ++k) uniform = out_cap[idx[k]] == out_cap[idx[0]];
     if (!uniform) std::stable_sort(idx.begin(), idx.end(), [&](uint32_t a, uint32_t b) { return out_cap[a] > out_cap[b]; });
+}
+
+// One launch on the context's stream (the image stages' device-pointer form, the Adler-32 launches): the shard locked and its device
+// current; before() -- what has to be enqueued in front of the first event, PZG_RC_OK or what the call returns --; launch(stream)
+// between the shard's two events; the wait, unless PZG_ASYNC.  (launch_device is not one of these: it records more events in between.)
+template <class Before, class Launch>
+int stream_launch(pzg_ctx *ctx, Shard &sh, uint32_t flags, Before &&before, Launch &&launch)
+{
+    std::lock_guard<std::mutex> g(sh.mu);
+    HIP_TRY(ctx, hipSetDevice(sh.device));
+    if (const int rc = before(); rc != PZG_RC_OK) return rc;
+    HIP_TRY(ctx, hipEventRecord(sh.ev0, sh.stream));
+    HIP_TRY(ctx, launch(sh.stream));
+    HIP_TRY(ctx, hipEventRecord(sh.ev1, sh.stream));
+    sh.timed = true;
+    sh.last_was_host = false;
+    if (!(flags & PZG_ASYNC)) HIP_TRY(ctx, hipStreamSynchronize(sh.stream));
+    return PZG_RC_OK;
+}
+inline int nothing_before() { return PZG_RC_OK; }
+
+// ---- the image stages (pzg_unfilter_many, pzg_adam7_many, pzg_expand_many).  What all three take: one device, PZG_DEVICE_PTRS, PZG_ASYNC with it
+inline bool stage_call_ok(const pzg_ctx *ctx, uint32_t n, uint32_t flags)
+{
+    return ctx_live(ctx) && n != 0 && !(flags & ~(PZG_DEVICE_PTRS | PZG_ASYNC)) && (!(flags & PZG_ASYNC) || (flags & PZG_DEVICE_PTRS)) && ctx->shards.size() == 1;
+}
+
+// the rows of an image the kernel delivered (image_stage_host): those in front of a failure, or all or none
+inline uint32_t rows_before_failure(int32_t status, uint32_t detail0, uint32_t rows) { return status == PZG_OK ? rows : detail0; }
+inline uint32_t rows_all_or_none(int32_t status, uint32_t, uint32_t rows) { return status == PZG_OK ? rows : 0u; }
+
+// The host-pointer form of an image stage, on lane 0.  The spans of src and dst that the images cover (pzg_stage_span.h) travel
+// through the lane's arenas, each at its place modulo 16; with them the metadata block: `meta` -- what the stage took for its own
+// arrays -- and behind it the statuses and details.  Of dst only the rows the kernel delivered -- nothing else -- are copied from the
+// staged span into the caller's memory.  A stage gives extent(i), image i as a pzg::StageExtent; fill(hm, dm, spans, a), which writes its
+// arrays into the host's copy hm of the block and points a's own members at the device's copy dm; its launcher; its delivered-row rule.
+template <class Args, class Extent, class Fill, class Delivered>
+int image_stage_host(pzg_ctx *ctx, const char *name, uint32_t n, const uint8_t *src_base, uint8_t *dst_base, int32_t *status, uint32_t *detail,
+                     const pzg::MetaCursor &meta, Extent &&extent, Fill &&fill, hipError_t (*launch)(const Args &, hipStream_t), Delivered &&delivered)
+{
+    pzg::StageSpans sp;  // (this and `m`: declared before the LaneCall)
+    for (uint32_t i = 0; i < n; ++i) sp.add(extent(i));
+    if (sp.nothing()) {
+        for (uint32_t i = 0; i < n; ++i) status[i] = PZG_OK;
+        if (detail) memset(detail, 0, 8 * (size_t)n);
+        return PZG_RC_OK;
+    }
+    sp.s.normalise();
+    const pzg::MetaResults m(meta, n);
+    return guarded(ctx, name, [&]() -> int {
+        LaneCall call(ctx, *ctx->shards[0]);
+        if (call.rc != PZG_RC_OK) return call.rc;
+        Lane &ln = call.ln;
+        hipStream_t st = call.st;
+        int rc;
+        const size_t s_bytes = sp.s.size(), d_bytes = sp.d.size();
+        if ((rc = arena_reserve(ctx, ln.d_in[0], s_bytes + 64)) != PZG_RC_OK) return rc;
+        if ((rc = arena_reserve(ctx, ln.d_out[0], d_bytes + 64)) != PZG_RC_OK) return rc;
+        if ((rc = arena_reserve(ctx, ln.d_meta[0], m.m_all)) != PZG_RC_OK) return rc;
+        if ((rc = pinned_reserve(ctx, ln.h_meta[0], m.m_all)) != PZG_RC_OK) return rc;
+        if ((rc = pinned_reserve(ctx, ln.h_out[0], d_bytes + 64)) != PZG_RC_OK) return rc;
+        uint8_t *hm = ln.h_meta[0].p, *dm = (uint8_t *)ln.d_meta[0].p;
+        uint8_t *d_src = (uint8_t *)ln.d_in[0].p + sp.s.skew(src_base);
+        Args a{};
+        a.src_base = d_src;
+        a.dst_base = (uint8_t *)ln.d_out[0].p + sp.d.skew(dst_base);
+        a.status = m.status.in(dm);
+        a.detail = m.detail.in(dm);
+        a.n = n;
+        fill(hm, dm, sp, a);
+        HIP_TRY(ctx, hipMemcpyAsync(dm, hm, m.m_in, hipMemcpyHostToDevice, st));
+        if (s_bytes) HIP_TRY(ctx, hipMemcpyAsync(d_src, src_base + sp.s.lo, s_bytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, call.begin_timed());
+        HIP_TRY(ctx, launch(a, st));
+        HIP_TRY(ctx, call.end_timed());
+        HIP_TRY(ctx, hipMemcpyAsync(m.status.in(hm), m.status.in(dm), m.m_all - m.m_in, hipMemcpyDeviceToHost, st));  // (the details with them)
+        HIP_TRY(ctx, hipMemcpyAsync(ln.h_out[0].p, a.dst_base, d_bytes, hipMemcpyDeviceToHost, st));
+        if ((rc = call.finish()) != PZG_RC_OK) return rc;
+        const int32_t *h_status = m.status.in(hm);
+        const uint32_t *h_detail = m.detail.in(hm);
+        memcpy(status, h_status, 4 * (size_t)n);
+        if (detail) memcpy(detail, h_detail, 8 * (size_t)n);
+        for (uint32_t i = 0; i < n; ++i) {
+            const pzg::StageExtent e = extent(i);
+            sp.copy_back(e, delivered(h_status[i], h_detail[2 * (size_t)i], e.rows), ln.h_out[0].p, dst_base);
+        }
+        return PZG_RC_OK;
+    });
 }
 
 }  // namespace
@@ -1786,222 +1875,101 @@ int pzg_gzip_layout(pzg_ctx *ctx, const uint8_t *in, uint64_t in_len, const uint
     });
 }
 
-// Scanline unfiltering (unfilter_core.h): the device-pointer form is one launch on the context's stream; the host-pointer form stages
-// the span of src that holds the images, the arrays and the span of dst that holds the extents through lane 0's arenas, and copies
-// the delivered rows -- nothing else -- from the staged span into the caller's dst.
+// The three image stages: the device-pointer form is one stream_launch, the host-pointer form image_stage_host.
+// Scanline unfiltering (unfilter_core.h).  An image whose src_len is 0 reads nothing: its src_off does not count for the span.  Of an
+// image that fails the rows in front of the failure are delivered.
 int pzg_unfilter_many(pzg_ctx *ctx, const uint8_t *src_base, const uint64_t *src_off, const uint64_t *src_len, uint8_t *dst_base, const uint64_t *dst_off,
                       const uint64_t *dst_stride, const uint32_t *row_bytes, const uint32_t *height, const uint8_t *bpp, int32_t *status,
                       uint32_t *detail, uint32_t n, uint32_t flags)
 {
     static_assert(pzg::Unfilter::ST_FILTER == PZG_E_FILTER && pzg::Unfilter::ST_TRUNCATED == PZG_E_TRUNCATED && pzg::Unfilter::ST_OK == PZG_OK,
                   "the core's statuses are the header's");
-    if (!ctx_live(ctx) || n == 0) return PZG_RC_BAD_ARG;
-    if ((flags & ~(PZG_DEVICE_PTRS | PZG_ASYNC)) || ((flags & PZG_ASYNC) && !(flags & PZG_DEVICE_PTRS))) return PZG_RC_BAD_ARG;
-    if (ctx->shards.size() != 1) return PZG_RC_BAD_ARG;
-    if (!src_base || !src_off || !src_len || !dst_base || !dst_off || !dst_stride || !row_bytes || !height || !bpp || !status) return PZG_RC_BAD_ARG;
-    Shard &sh = *ctx->shards[0];
+    if (!stage_call_ok(ctx, n, flags) || !src_base || !src_off || !src_len || !dst_base || !dst_off || !dst_stride || !row_bytes || !height || !bpp || !status) return PZG_RC_BAD_ARG;
     if (flags & PZG_DEVICE_PTRS)
         return guarded(ctx, "pzg_unfilter_many", [&]() -> int {
-            std::lock_guard<std::mutex> g(sh.mu);
-            HIP_TRY(ctx, hipSetDevice(sh.device));
-            pzg::UnfilterArgs a{src_base, src_off, src_len, dst_base, dst_off, dst_stride, row_bytes, height, bpp, status, detail, n};
-            HIP_TRY(ctx, hipEventRecord(sh.ev0, sh.stream));
-            HIP_TRY(ctx, pzg::launch_unfilter(a, sh.stream));
-            HIP_TRY(ctx, hipEventRecord(sh.ev1, sh.stream));
-            sh.timed = true;
-            sh.last_was_host = false;
-            if (!(flags & PZG_ASYNC)) HIP_TRY(ctx, hipStreamSynchronize(sh.stream));
-            return PZG_RC_OK;
+            const pzg::UnfilterArgs a{src_base, src_off, src_len, dst_base, dst_off, dst_stride, row_bytes, height, bpp, status, detail, n};
+            return stream_launch(ctx, *ctx->shards[0], flags, nothing_before, [&](hipStream_t s) { return pzg::launch_unfilter(a, s); });
         });
-    // host pointers: the spans, and what the device form leaves to the kernel
-    uint64_t s_lo = ~0ull, s_hi = 0, d_lo = ~0ull, d_hi = 0;
-    for (uint32_t i = 0; i < n; ++i) {
-        if (row_bytes[i] == 0u || height[i] == 0u) continue;
-        if (!pzg::Unfilter::bpp_ok(bpp[i]) || dst_stride[i] < row_bytes[i]) return PZG_RC_BAD_ARG;
-        const uint64_t d_end = dst_off[i] + (uint64_t)(height[i] - 1u) * dst_stride[i] + row_bytes[i];
-        d_lo = std::min(d_lo, dst_off[i]);
-        d_hi = std::max(d_hi, d_end);
-        if (src_len[i] == 0u) continue;
-        s_lo = std::min(s_lo, src_off[i]);
-        s_hi = std::max(s_hi, src_off[i] + src_len[i]);
-    }
-    if (d_lo > d_hi) {  // nothing but empty images
-        for (uint32_t i = 0; i < n; ++i) status[i] = PZG_OK;
-        if (detail) memset(detail, 0, 8 * (size_t)n);
-        return PZG_RC_OK;
-    }
-    if (s_lo > s_hi) s_lo = s_hi = 0;
-    return guarded(ctx, "pzg_unfilter_many", [&]() -> int {
-        LaneCall call(ctx, sh);
-        if (call.rc != PZG_RC_OK) return call.rc;
-        Lane &ln = call.ln;
-        hipStream_t st = call.st;
-        int rc;
-        // the spans keep their places modulo 16: a row is fetched and stored at the alignment the caller gave it
-        const size_t s_skew = (size_t)((uintptr_t)(src_base + s_lo) & 15u), d_skew = (size_t)((uintptr_t)(dst_base + d_lo) & 15u);
-        const size_t s_bytes = (size_t)(s_hi - s_lo), d_bytes = (size_t)(d_hi - d_lo);
-        const size_t row8 = pad256(8 * (size_t)n), row4 = pad256(4 * (size_t)n);
-        const size_t m_in = 4 * row8 + 2 * row4 + pad256(n), m_all = m_in + row4 + pad256(8 * (size_t)n);
-        if ((rc = arena_reserve(ctx, ln.d_in[0], s_bytes + 64)) != PZG_RC_OK) return rc;
-        if ((rc = arena_reserve(ctx, ln.d_out[0], d_bytes + 64)) != PZG_RC_OK) return rc;
-        if ((rc = arena_reserve(ctx, ln.d_meta[0], m_all)) != PZG_RC_OK) return rc;
-        if ((rc = pinned_reserve(ctx, ln.h_meta[0], m_all)) != PZG_RC_OK) return rc;
-        if ((rc = pinned_reserve(ctx, ln.h_out[0], d_bytes + 64)) != PZG_RC_OK) return rc;
-        uint8_t *hm = ln.h_meta[0].p, *dm = (uint8_t *)ln.d_meta[0].p;
-        uint64_t *h_soff = (uint64_t *)(void *)hm, *h_slen = (uint64_t *)(void *)(hm + row8), *h_doff = (uint64_t *)(void *)(hm + 2 * row8);
-        for (uint32_t i = 0; i < n; ++i) {
-            const bool empty = row_bytes[i] == 0u || height[i] == 0u;
-            h_soff[i] = empty || src_len[i] == 0u ? 0u : src_off[i] - s_lo;
-            h_slen[i] = src_len[i];
-            h_doff[i] = empty ? 0u : dst_off[i] - d_lo;
-        }
-        memcpy(hm + 3 * row8, dst_stride, 8 * (size_t)n);
-        memcpy(hm + 4 * row8, row_bytes, 4 * (size_t)n);
-        memcpy(hm + 4 * row8 + row4, height, 4 * (size_t)n);
-        memcpy(hm + 4 * row8 + 2 * row4, bpp, n);
-        HIP_TRY(ctx, hipMemcpyAsync(dm, hm, m_in, hipMemcpyHostToDevice, st));
-        if (s_bytes) HIP_TRY(ctx, hipMemcpyAsync((uint8_t *)ln.d_in[0].p + s_skew, src_base + s_lo, s_bytes, hipMemcpyHostToDevice, st));
-        pzg::UnfilterArgs a{};
-        a.src_base = (const uint8_t *)ln.d_in[0].p + s_skew;
-        a.src_off = (const uint64_t *)(void *)dm;
-        a.src_len = (const uint64_t *)(void *)(dm + row8);
-        a.dst_base = (uint8_t *)ln.d_out[0].p + d_skew;
-        a.dst_off = (const uint64_t *)(void *)(dm + 2 * row8);
-        a.dst_stride = (const uint64_t *)(void *)(dm + 3 * row8);
-        a.row_bytes = (const uint32_t *)(void *)(dm + 4 * row8);
-        a.height = (const uint32_t *)(void *)(dm + 4 * row8 + row4);
-        a.bpp = dm + 4 * row8 + 2 * row4;
-        a.status = (int32_t *)(void *)(dm + m_in);
-        a.detail = (uint32_t *)(void *)(dm + m_in + row4);
-        a.n = n;
-        HIP_TRY(ctx, call.begin_timed());
-        HIP_TRY(ctx, pzg::launch_unfilter(a, st));
-        HIP_TRY(ctx, call.end_timed());
-        HIP_TRY(ctx, hipMemcpyAsync(hm + m_in, dm + m_in, m_all - m_in, hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipMemcpyAsync(ln.h_out[0].p, a.dst_base, d_bytes, hipMemcpyDeviceToHost, st));
-        if ((rc = call.finish()) != PZG_RC_OK) return rc;
-        const int32_t *h_status = (const int32_t *)(const void *)(hm + m_in);
-        const uint32_t *h_detail = (const uint32_t *)(const void *)(hm + m_in + row4);
-        memcpy(status, h_status, 4 * (size_t)n);
-        if (detail) memcpy(detail, h_detail, 8 * (size_t)n);
-        for (uint32_t i = 0; i < n; ++i) {  // the rows the kernel delivered
-            if (row_bytes[i] == 0u || height[i] == 0u) continue;
-            const uint32_t rows = h_status[i] == PZG_OK ? height[i] : std::min(h_detail[2 * (size_t)i], height[i]);
-            for (uint32_t r = 0; r < rows; ++r) {
-                const uint64_t at = dst_off[i] + (uint64_t)r * dst_stride[i];
-                memcpy(dst_base + at, ln.h_out[0].p + (at - d_lo), row_bytes[i]);
+    // host pointers: what the device form leaves to the kernel
+    const auto empty = [&](uint32_t i) { return row_bytes[i] == 0u || height[i] == 0u; };
+    for (uint32_t i = 0; i < n; ++i)
+        if (!empty(i) && (!pzg::Unfilter::bpp_ok(bpp[i]) || dst_stride[i] < row_bytes[i])) return PZG_RC_BAD_ARG;
+    pzg::MetaCursor c;
+    const auto m_soff = c.take<uint64_t>(n), m_slen = c.take<uint64_t>(n), m_doff = c.take<uint64_t>(n), m_stride = c.take<uint64_t>(n);
+    const auto m_rb = c.take<uint32_t>(n), m_height = c.take<uint32_t>(n);
+    const auto m_bpp = c.take<uint8_t>(n);
+    const auto extent = [&](uint32_t i) { return pzg::StageExtent{src_off[i], src_len[i], dst_off[i], dst_stride[i], row_bytes[i], height[i], empty(i)}; };
+    return image_stage_host(
+        ctx, "pzg_unfilter_many", n, src_base, dst_base, status, detail, c, extent,
+        [&](uint8_t *hm, uint8_t *dm, const pzg::StageSpans &sp, pzg::UnfilterArgs &a) {
+            for (uint32_t i = 0; i < n; ++i) {
+                m_soff.in(hm)[i] = sp.src_at(extent(i));
+                m_slen.in(hm)[i] = src_len[i];
+                m_doff.in(hm)[i] = sp.dst_at(extent(i));
             }
-        }
-        return PZG_RC_OK;
-    });
+            memcpy(m_stride.in(hm), dst_stride, 8 * (size_t)n);
+            memcpy(m_rb.in(hm), row_bytes, 4 * (size_t)n);
+            memcpy(m_height.in(hm), height, 4 * (size_t)n);
+            memcpy(m_bpp.in(hm), bpp, n);
+            a.src_off = m_soff.in(dm);
+            a.src_len = m_slen.in(dm);
+            a.dst_off = m_doff.in(dm);
+            a.dst_stride = m_stride.in(dm);
+            a.row_bytes = m_rb.in(dm);
+            a.height = m_height.in(dm);
+            a.bpp = m_bpp.in(dm);
+        },
+        pzg::launch_unfilter, rows_before_failure);
 }
 
-// Adam7 deinterlacing (adam7_core.h): the two forms of pzg_unfilter_many.  The host-pointer form stages the span of src that holds the
-// images' passes, the arrays and the span of dst that holds the extents, and copies the rows of the images -- nothing else -- from the
-// staged span into the caller's dst.
+// Adam7 deinterlacing (adam7_core.h).  An image's source is its seven passes, dense; its rows are delivered all or none.
 int pzg_adam7_many(pzg_ctx *ctx, const uint8_t *src_base, const uint64_t *src_off, uint8_t *dst_base, const uint64_t *dst_off, const uint64_t *dst_stride,
                    const uint32_t *width, const uint32_t *height, const uint8_t *pixel_bits, int32_t *status, uint32_t *detail, uint32_t n, uint32_t flags)
 {
     static_assert(pzg::Adam7::ST_FILTER == PZG_E_FILTER && pzg::Adam7::ST_OK == PZG_OK, "the core's statuses are the header's");
-    if (!ctx_live(ctx) || n == 0) return PZG_RC_BAD_ARG;
-    if ((flags & ~(PZG_DEVICE_PTRS | PZG_ASYNC)) || ((flags & PZG_ASYNC) && !(flags & PZG_DEVICE_PTRS))) return PZG_RC_BAD_ARG;
-    if (ctx->shards.size() != 1) return PZG_RC_BAD_ARG;
-    if (!src_base || !src_off || !dst_base || !dst_off || !dst_stride || !width || !height || !pixel_bits || !status) return PZG_RC_BAD_ARG;
-    Shard &sh = *ctx->shards[0];
+    using A7 = pzg::Adam7;
+    if (!stage_call_ok(ctx, n, flags) || !src_base || !src_off || !dst_base || !dst_off || !dst_stride || !width || !height || !pixel_bits || !status) return PZG_RC_BAD_ARG;
     if (flags & PZG_DEVICE_PTRS)
         return guarded(ctx, "pzg_adam7_many", [&]() -> int {
-            std::lock_guard<std::mutex> g(sh.mu);
-            HIP_TRY(ctx, hipSetDevice(sh.device));
-            pzg::Adam7Args a{src_base, src_off, dst_base, dst_off, dst_stride, width, height, pixel_bits, status, detail, n};
-            HIP_TRY(ctx, hipEventRecord(sh.ev0, sh.stream));
-            HIP_TRY(ctx, pzg::launch_adam7(a, sh.stream));
-            HIP_TRY(ctx, hipEventRecord(sh.ev1, sh.stream));
-            sh.timed = true;
-            sh.last_was_host = false;
-            if (!(flags & PZG_ASYNC)) HIP_TRY(ctx, hipStreamSynchronize(sh.stream));
-            return PZG_RC_OK;
+            const pzg::Adam7Args a{src_base, src_off, dst_base, dst_off, dst_stride, width, height, pixel_bits, status, detail, n};
+            return stream_launch(ctx, *ctx->shards[0], flags, nothing_before, [&](hipStream_t s) { return pzg::launch_adam7(a, s); });
         });
-    // host pointers: the spans, and what the device form leaves to the kernel
-    uint64_t s_lo = ~0ull, s_hi = 0, d_lo = ~0ull, d_hi = 0;
-    for (uint32_t i = 0; i < n; ++i) {
-        if (width[i] == 0u || height[i] == 0u) continue;
-        if (!pzg::Adam7::geometry_ok(dst_stride[i], width[i], height[i], pixel_bits[i])) return PZG_RC_BAD_ARG;
-        const uint64_t d_end = dst_off[i] + (uint64_t)(height[i] - 1u) * dst_stride[i] + pzg::Adam7::bytes_of(width[i], pixel_bits[i]);
-        d_lo = std::min(d_lo, dst_off[i]);
-        d_hi = std::max(d_hi, d_end);
-        s_lo = std::min(s_lo, src_off[i]);
-        s_hi = std::max(s_hi, src_off[i] + pzg::Adam7::src_extent(width[i], height[i], pixel_bits[i]));
-    }
-    if (d_lo > d_hi) {  // nothing but empty images
-        for (uint32_t i = 0; i < n; ++i) status[i] = PZG_OK;
-        if (detail) memset(detail, 0, 8 * (size_t)n);
-        return PZG_RC_OK;
-    }
-    return guarded(ctx, "pzg_adam7_many", [&]() -> int {
-        LaneCall call(ctx, sh);
-        if (call.rc != PZG_RC_OK) return call.rc;
-        Lane &ln = call.ln;
-        hipStream_t st = call.st;
-        int rc;
-        // the spans keep their places modulo 16: a row is fetched and stored at the alignment the caller gave it
-        const size_t s_skew = (size_t)((uintptr_t)(src_base + s_lo) & 15u), d_skew = (size_t)((uintptr_t)(dst_base + d_lo) & 15u);
-        const size_t s_bytes = (size_t)(s_hi - s_lo), d_bytes = (size_t)(d_hi - d_lo);
-        const size_t row8 = pad256(8 * (size_t)n), row4 = pad256(4 * (size_t)n);
-        const size_t m_in = 3 * row8 + 2 * row4 + pad256(n), m_all = m_in + row4 + pad256(8 * (size_t)n);
-        if ((rc = arena_reserve(ctx, ln.d_in[0], s_bytes + 64)) != PZG_RC_OK) return rc;
-        if ((rc = arena_reserve(ctx, ln.d_out[0], d_bytes + 64)) != PZG_RC_OK) return rc;
-        if ((rc = arena_reserve(ctx, ln.d_meta[0], m_all)) != PZG_RC_OK) return rc;
-        if ((rc = pinned_reserve(ctx, ln.h_meta[0], m_all)) != PZG_RC_OK) return rc;
-        if ((rc = pinned_reserve(ctx, ln.h_out[0], d_bytes + 64)) != PZG_RC_OK) return rc;
-        uint8_t *hm = ln.h_meta[0].p, *dm = (uint8_t *)ln.d_meta[0].p;
-        uint64_t *h_soff = (uint64_t *)(void *)hm, *h_doff = (uint64_t *)(void *)(hm + row8);
-        for (uint32_t i = 0; i < n; ++i) {
-            const bool empty = width[i] == 0u || height[i] == 0u;
-            h_soff[i] = empty ? 0u : src_off[i] - s_lo;
-            h_doff[i] = empty ? 0u : dst_off[i] - d_lo;
-        }
-        memcpy(hm + 2 * row8, dst_stride, 8 * (size_t)n);
-        memcpy(hm + 3 * row8, width, 4 * (size_t)n);
-        memcpy(hm + 3 * row8 + row4, height, 4 * (size_t)n);
-        memcpy(hm + 3 * row8 + 2 * row4, pixel_bits, n);
-        HIP_TRY(ctx, hipMemcpyAsync(dm, hm, m_in, hipMemcpyHostToDevice, st));
-        if (s_bytes) HIP_TRY(ctx, hipMemcpyAsync((uint8_t *)ln.d_in[0].p + s_skew, src_base + s_lo, s_bytes, hipMemcpyHostToDevice, st));
-        pzg::Adam7Args a{};
-        a.src_base = (const uint8_t *)ln.d_in[0].p + s_skew;
-        a.src_off = (const uint64_t *)(void *)dm;
-        a.dst_base = (uint8_t *)ln.d_out[0].p + d_skew;
-        a.dst_off = (const uint64_t *)(void *)(dm + row8);
-        a.dst_stride = (const uint64_t *)(void *)(dm + 2 * row8);
-        a.width = (const uint32_t *)(void *)(dm + 3 * row8);
-        a.height = (const uint32_t *)(void *)(dm + 3 * row8 + row4);
-        a.pixel_bits = dm + 3 * row8 + 2 * row4;
-        a.status = (int32_t *)(void *)(dm + m_in);
-        a.detail = (uint32_t *)(void *)(dm + m_in + row4);
-        a.n = n;
-        HIP_TRY(ctx, call.begin_timed());
-        HIP_TRY(ctx, pzg::launch_adam7(a, st));
-        HIP_TRY(ctx, call.end_timed());
-        HIP_TRY(ctx, hipMemcpyAsync(hm + m_in, dm + m_in, m_all - m_in, hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipMemcpyAsync(ln.h_out[0].p, a.dst_base, d_bytes, hipMemcpyDeviceToHost, st));
-        if ((rc = call.finish()) != PZG_RC_OK) return rc;
-        const int32_t *h_status = (const int32_t *)(const void *)(hm + m_in);
-        memcpy(status, h_status, 4 * (size_t)n);
-        if (detail) memcpy(detail, hm + m_in + row4, 8 * (size_t)n);
-        for (uint32_t i = 0; i < n; ++i) {  // the rows the kernel delivered
-            if (width[i] == 0u || height[i] == 0u || h_status[i] != PZG_OK) continue;
-            const uint64_t rb = pzg::Adam7::bytes_of(width[i], pixel_bits[i]);
-            for (uint32_t r = 0; r < height[i]; ++r) {
-                const uint64_t at = dst_off[i] + (uint64_t)r * dst_stride[i];
-                memcpy(dst_base + at, ln.h_out[0].p + (at - d_lo), rb);
+    // host pointers: what the device form leaves to the kernel
+    const auto empty = [&](uint32_t i) { return width[i] == 0u || height[i] == 0u; };
+    for (uint32_t i = 0; i < n; ++i)
+        if (!empty(i) && !A7::geometry_ok(dst_stride[i], width[i], height[i], pixel_bits[i])) return PZG_RC_BAD_ARG;
+    pzg::MetaCursor c;
+    const auto m_soff = c.take<uint64_t>(n), m_doff = c.take<uint64_t>(n), m_stride = c.take<uint64_t>(n);
+    const auto m_width = c.take<uint32_t>(n), m_height = c.take<uint32_t>(n);
+    const auto m_bits = c.take<uint8_t>(n);
+    const auto extent = [&](uint32_t i) {
+        if (empty(i)) return pzg::StageExtent{};
+        return pzg::StageExtent{src_off[i], A7::src_extent(width[i], height[i], pixel_bits[i]), dst_off[i], dst_stride[i], A7::bytes_of(width[i], pixel_bits[i]),
+                                height[i], false};
+    };
+    return image_stage_host(
+        ctx, "pzg_adam7_many", n, src_base, dst_base, status, detail, c, extent,
+        [&](uint8_t *hm, uint8_t *dm, const pzg::StageSpans &sp, pzg::Adam7Args &a) {
+            for (uint32_t i = 0; i < n; ++i) {
+                m_soff.in(hm)[i] = sp.src_at(extent(i));
+                m_doff.in(hm)[i] = sp.dst_at(extent(i));
             }
-        }
-        return PZG_RC_OK;
-    });
+            memcpy(m_stride.in(hm), dst_stride, 8 * (size_t)n);
+            memcpy(m_width.in(hm), width, 4 * (size_t)n);
+            memcpy(m_height.in(hm), height, 4 * (size_t)n);
+            memcpy(m_bits.in(hm), pixel_bits, n);
+            a.src_off = m_soff.in(dm);
+            a.dst_off = m_doff.in(dm);
+            a.dst_stride = m_stride.in(dm);
+            a.width = m_width.in(dm);
+            a.height = m_height.in(dm);
+            a.pixel_bits = m_bits.in(dm);
+        },
+        pzg::launch_adam7, rows_all_or_none);
 }
 
-// Pixel expansion (expand_core.h): the two forms of pzg_adam7_many.  The host-pointer form stages the span of src that holds the
-// images' rows, the palette entries they name, the descriptors -- their offsets counted from the spans' starts -- and the span of dst
-// that holds the extents, and copies the rows of the images that are PZG_OK -- nothing else -- from the staged span into the caller's dst.
+// Pixel expansion (expand_core.h).  The descriptors travel with their offsets counted from the spans' starts; so do the palette
+// entries they name, and the zeroed scratch.  An image's rows are delivered all or none.
 int pzg_expand_many(pzg_ctx *ctx, const uint8_t *src_base, uint8_t *dst_base, const uint32_t *palette_base, const pzg_expand_desc *desc, int32_t *status,
                     uint32_t *detail, uint32_t n, uint32_t flags)
 {
@@ -2016,110 +1984,59 @@ int pzg_expand_many(pzg_ctx *ctx, const uint8_t *src_base, uint8_t *dst_base, co
                       offsetof(E::Desc, bit_depth) == offsetof(pzg_expand_desc, bit_depth) && offsetof(E::Desc, out_format) == offsetof(pzg_expand_desc, out_format) &&
                       offsetof(E::Desc, has_key) == offsetof(pzg_expand_desc, has_key),
                   "the core's descriptor is the header's");
-    if (!ctx_live(ctx) || n == 0) return PZG_RC_BAD_ARG;
-    if ((flags & ~(PZG_DEVICE_PTRS | PZG_ASYNC)) || ((flags & PZG_ASYNC) && !(flags & PZG_DEVICE_PTRS))) return PZG_RC_BAD_ARG;
-    if (ctx->shards.size() != 1) return PZG_RC_BAD_ARG;
-    if (!src_base || !dst_base || !desc || !status) return PZG_RC_BAD_ARG;
-    Shard &sh = *ctx->shards[0];
+    if (!stage_call_ok(ctx, n, flags) || !src_base || !dst_base || !desc || !status) return PZG_RC_BAD_ARG;
     if (flags & PZG_DEVICE_PTRS)
         return guarded(ctx, "pzg_expand_many", [&]() -> int {
-            std::lock_guard<std::mutex> g(sh.mu);
-            HIP_TRY(ctx, hipSetDevice(sh.device));
-            // (its own scratch: launches on different streams may overlap; arena_reserve frees a slot's old one through hipFree only)
-            Arena &scr = sh.a_expand[sh.next_counter.fetch_add(1u) % COUNTER_SLOTS];
-            const int rc = arena_reserve(ctx, scr, pzg::expand_scratch_bytes(n));
-            if (rc != PZG_RC_OK) return rc;
-            pzg::ExpandArgs a{src_base, dst_base, palette_base, desc, (uint64_t *)scr.p, status, detail, n};
-            HIP_TRY(ctx, hipMemsetAsync(scr.p, 0, pzg::expand_scratch_bytes(n), sh.stream));
-            HIP_TRY(ctx, hipEventRecord(sh.ev0, sh.stream));
-            HIP_TRY(ctx, pzg::launch_expand(a, sh.stream));
-            HIP_TRY(ctx, hipEventRecord(sh.ev1, sh.stream));
-            sh.timed = true;
-            sh.last_was_host = false;
-            if (!(flags & PZG_ASYNC)) HIP_TRY(ctx, hipStreamSynchronize(sh.stream));
-            return PZG_RC_OK;
+            Shard &sh = *ctx->shards[0];
+            pzg::ExpandArgs a{src_base, dst_base, palette_base, desc, nullptr, status, detail, n};
+            const auto zeroed_scratch = [&]() -> int {
+                // (its own scratch: launches on different streams may overlap; arena_reserve frees a slot's old one through hipFree only)
+                Arena &scr = sh.a_expand[sh.next_counter.fetch_add(1u) % COUNTER_SLOTS];
+                const int rc = arena_reserve(ctx, scr, pzg::expand_scratch_bytes(n));
+                if (rc != PZG_RC_OK) return rc;
+                a.scratch = (uint64_t *)scr.p;
+                HIP_TRY(ctx, hipMemsetAsync(scr.p, 0, pzg::expand_scratch_bytes(n), sh.stream));
+                return PZG_RC_OK;
+            };
+            return stream_launch(ctx, sh, flags, zeroed_scratch, [&](hipStream_t s) { return pzg::launch_expand(a, s); });
         });
-    // host pointers: the spans, and what the device form leaves to the kernel
+    // host pointers: what the device form leaves to the kernel, and the span of the palette
     const E::Desc *hd = (const E::Desc *)(const void *)desc;
-    uint64_t s_lo = ~0ull, s_hi = 0, d_lo = ~0ull, d_hi = 0, p_lo = ~0ull, p_hi = 0;
+    const auto empty = [&](uint32_t i) { return hd[i].width == 0u || hd[i].height == 0u; };
+    pzg::Span pal;
     for (uint32_t i = 0; i < n; ++i) {
+        if (empty(i)) continue;
+        if (!E::geometry_ok(hd[i]) || (hd[i].color_type == 3u && !palette_base)) return PZG_RC_BAD_ARG;
+        if (hd[i].color_type == 3u) pal.add(hd[i].pal_off, hd[i].pal_len);
+    }
+    pal.normalise();
+    pzg::MetaCursor c;
+    const auto m_desc = c.take<E::Desc>(n);
+    const auto m_pal = c.take<uint32_t>(pal.size());
+    const auto m_scratch = c.take<uint64_t>(pzg::expand_scratch_bytes(n) / 8u);  // (it goes up zeroed with the rest)
+    const auto extent = [&](uint32_t i) {
         const E::Desc &D = hd[i];
-        if (D.width == 0u || D.height == 0u) continue;
-        if (!E::geometry_ok(D) || (D.color_type == 3u && !palette_base)) return PZG_RC_BAD_ARG;
-        const uint64_t rows = D.height - 1u;
-        d_lo = std::min(d_lo, D.dst_off);
-        d_hi = std::max(d_hi, D.dst_off + rows * D.dst_stride + E::dst_row_bytes(D.width, D.out_format));
-        s_lo = std::min(s_lo, D.src_off);
-        s_hi = std::max(s_hi, D.src_off + rows * D.src_stride + E::src_row_bytes(D.width, D.color_type, D.bit_depth));
-        if (D.color_type == 3u) {
-            p_lo = std::min(p_lo, (uint64_t)D.pal_off);
-            p_hi = std::max(p_hi, (uint64_t)D.pal_off + D.pal_len);
-        }
-    }
-    if (d_lo > d_hi) {  // nothing but empty images
-        for (uint32_t i = 0; i < n; ++i) status[i] = PZG_OK;
-        if (detail) memset(detail, 0, 8 * (size_t)n);
-        return PZG_RC_OK;
-    }
-    if (p_lo > p_hi) p_lo = p_hi = 0;
-    return guarded(ctx, "pzg_expand_many", [&]() -> int {
-        LaneCall call(ctx, sh);
-        if (call.rc != PZG_RC_OK) return call.rc;
-        Lane &ln = call.ln;
-        hipStream_t st = call.st;
-        int rc;
-        // the spans keep their places modulo 16: a row is fetched and stored at the alignment the caller gave it
-        const size_t s_skew = (size_t)((uintptr_t)(src_base + s_lo) & 15u), d_skew = (size_t)((uintptr_t)(dst_base + d_lo) & 15u);
-        const size_t s_bytes = (size_t)(s_hi - s_lo), d_bytes = (size_t)(d_hi - d_lo);
-        const size_t m_desc = pad256(sizeof(E::Desc) * (size_t)n), m_pal = pad256(4 * (size_t)(p_hi - p_lo)), m_scr = pad256(pzg::expand_scratch_bytes(n));
-        const size_t row4 = pad256(4 * (size_t)n), m_in = m_desc + m_pal + m_scr, m_all = m_in + row4 + pad256(8 * (size_t)n);
-        if ((rc = arena_reserve(ctx, ln.d_in[0], s_bytes + 64)) != PZG_RC_OK) return rc;
-        if ((rc = arena_reserve(ctx, ln.d_out[0], d_bytes + 64)) != PZG_RC_OK) return rc;
-        if ((rc = arena_reserve(ctx, ln.d_meta[0], m_all)) != PZG_RC_OK) return rc;
-        if ((rc = pinned_reserve(ctx, ln.h_meta[0], m_all)) != PZG_RC_OK) return rc;
-        if ((rc = pinned_reserve(ctx, ln.h_out[0], d_bytes + 64)) != PZG_RC_OK) return rc;
-        uint8_t *hm = ln.h_meta[0].p, *dm = (uint8_t *)ln.d_meta[0].p;
-        E::Desc *sd = (E::Desc *)(void *)hm;
-        for (uint32_t i = 0; i < n; ++i) {
-            sd[i] = hd[i];
-            const bool empty = hd[i].width == 0u || hd[i].height == 0u;
-            sd[i].src_off = empty ? 0u : hd[i].src_off - s_lo;
-            sd[i].dst_off = empty ? 0u : hd[i].dst_off - d_lo;
-            sd[i].pal_off = empty || hd[i].color_type != 3u ? 0u : (uint32_t)(hd[i].pal_off - p_lo);
-        }
-        if (p_hi > p_lo) memcpy(hm + m_desc, palette_base + p_lo, 4 * (size_t)(p_hi - p_lo));
-        memset(hm + m_desc + m_pal, 0, m_scr);  // (the scratch goes up zeroed with the rest)
-        HIP_TRY(ctx, hipMemcpyAsync(dm, hm, m_in, hipMemcpyHostToDevice, st));
-        HIP_TRY(ctx, hipMemcpyAsync((uint8_t *)ln.d_in[0].p + s_skew, src_base + s_lo, s_bytes, hipMemcpyHostToDevice, st));
-        pzg::ExpandArgs a{};
-        a.src_base = (const uint8_t *)ln.d_in[0].p + s_skew;
-        a.dst_base = (uint8_t *)ln.d_out[0].p + d_skew;
-        a.palette_base = (const uint32_t *)(void *)(dm + m_desc);
-        a.desc = dm;
-        a.scratch = (uint64_t *)(void *)(dm + m_desc + m_pal);
-        a.status = (int32_t *)(void *)(dm + m_in);
-        a.detail = (uint32_t *)(void *)(dm + m_in + row4);
-        a.n = n;
-        HIP_TRY(ctx, call.begin_timed());
-        HIP_TRY(ctx, pzg::launch_expand(a, st));
-        HIP_TRY(ctx, call.end_timed());
-        HIP_TRY(ctx, hipMemcpyAsync(hm + m_in, dm + m_in, m_all - m_in, hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipMemcpyAsync(ln.h_out[0].p, a.dst_base, d_bytes, hipMemcpyDeviceToHost, st));
-        if ((rc = call.finish()) != PZG_RC_OK) return rc;
-        const int32_t *h_status = (const int32_t *)(const void *)(hm + m_in);
-        memcpy(status, h_status, 4 * (size_t)n);
-        if (detail) memcpy(detail, hm + m_in + row4, 8 * (size_t)n);
-        for (uint32_t i = 0; i < n; ++i) {  // the rows the kernel delivered
-            const E::Desc &D = hd[i];
-            if (D.width == 0u || D.height == 0u || h_status[i] != PZG_OK) continue;
-            const uint64_t rb = E::dst_row_bytes(D.width, D.out_format);
-            for (uint32_t r = 0; r < D.height; ++r) {
-                const uint64_t at = D.dst_off + (uint64_t)r * D.dst_stride;
-                memcpy(dst_base + at, ln.h_out[0].p + (at - d_lo), rb);
+        if (empty(i)) return pzg::StageExtent{};
+        return pzg::StageExtent{D.src_off, (uint64_t)(D.height - 1u) * D.src_stride + E::src_row_bytes(D.width, D.color_type, D.bit_depth), D.dst_off, D.dst_stride,
+                                E::dst_row_bytes(D.width, D.out_format), D.height, false};
+    };
+    return image_stage_host(
+        ctx, "pzg_expand_many", n, src_base, dst_base, status, detail, c, extent,
+        [&](uint8_t *hm, uint8_t *dm, const pzg::StageSpans &sp, pzg::ExpandArgs &a) {
+            E::Desc *sd = m_desc.in(hm);
+            for (uint32_t i = 0; i < n; ++i) {
+                sd[i] = hd[i];
+                sd[i].src_off = sp.src_at(extent(i));
+                sd[i].dst_off = sp.dst_at(extent(i));
+                sd[i].pal_off = (uint32_t)pal.rebased(hd[i].pal_off, !empty(i) && hd[i].color_type == 3u);
             }
-        }
-        return PZG_RC_OK;
-    });
+            if (pal.size()) memcpy(m_pal.in(hm), palette_base + pal.lo, 4 * pal.size());
+            memset(m_scratch.in(hm), 0, pzg::expand_scratch_bytes(n));
+            a.palette_base = m_pal.in(dm);
+            a.desc = m_desc.in(dm);
+            a.scratch = m_scratch.in(dm);
+        },
+        pzg::launch_expand, rows_all_or_none);
 }
 
 int pzg_decompress_many_sharded(pzg_ctx *ctx, const pzg_device_batch *batches, uint32_t nbatches, uint32_t flags)
@@ -2754,22 +2671,21 @@ int pzg_adler32(pzg_ctx *ctx, const uint8_t *buf, uint64_t len, uint32_t init, u
     if ((flags & PZG_ASYNC) && !(flags & PZG_DEVICE_PTRS)) return PZG_RC_BAD_ARG;
     return guarded(ctx, "pzg_adler32", [&]() -> int {
         Shard &sh = *ctx->shards[0];
+        uint32_t *partials = nullptr;
+        const auto reserve_partials = [&]() -> int {  // (under the shard's lock)
+            const int r = arena_reserve(ctx, sh.a_adler, 12 * (size_t)(ADLER_MAX_WAVES + 4) + 16);
+            partials = (uint32_t *)sh.a_adler.p;
+            return r;
+        };
+        if (flags & PZG_DEVICE_PTRS)
+            return stream_launch(ctx, sh, flags, reserve_partials, [&](hipStream_t s) { return pzg::launch_adler32(buf, len, init, partials, ADLER_MAX_WAVES, out, s); });
+        // host pointers: the buffer goes up in front of the events, the sum comes down behind them, under one hold of the lock: not stream_launch's shape
         std::lock_guard<std::mutex> g(sh.mu);
         HIP_TRY(ctx, hipSetDevice(sh.device));
         int rc;
-        if ((rc = arena_reserve(ctx, sh.a_adler, 12 * (size_t)(ADLER_MAX_WAVES + 4) + 16)) != PZG_RC_OK) return rc;
-        uint32_t *partials = (uint32_t *)sh.a_adler.p;
+        if ((rc = reserve_partials()) != PZG_RC_OK) return rc;
         uint32_t *d_res = partials + 3 * (size_t)(ADLER_MAX_WAVES + 4);
         hipStream_t s = sh.stream;
-        if (flags & PZG_DEVICE_PTRS) {
-            HIP_TRY(ctx, hipEventRecord(sh.ev0, s));
-            HIP_TRY(ctx, pzg::launch_adler32(buf, len, init, partials, ADLER_MAX_WAVES, out, s));
-            HIP_TRY(ctx, hipEventRecord(sh.ev1, s));
-            sh.timed = true;
-            sh.last_was_host = false;
-            if (!(flags & PZG_ASYNC)) HIP_TRY(ctx, hipStreamSynchronize(s));
-            return PZG_RC_OK;
-        }
         const uint32_t skew = (uint32_t)((uintptr_t)buf & 15u);
         if ((rc = arena_reserve(ctx, sh.a_scratch, len + 64)) != PZG_RC_OK) return rc;
         uint8_t *d_buf = (uint8_t *)sh.a_scratch.p + skew;
@@ -2793,15 +2709,7 @@ int pzg_adler32_many(pzg_ctx *ctx, const uint8_t *base, const uint64_t *off, con
     if (n == 0) return PZG_RC_OK;
     return guarded(ctx, "pzg_adler32_many", [&]() -> int {
         Shard &sh = *ctx->shards[0];
-        std::lock_guard<std::mutex> g(sh.mu);
-        HIP_TRY(ctx, hipSetDevice(sh.device));
-        HIP_TRY(ctx, hipEventRecord(sh.ev0, sh.stream));
-        HIP_TRY(ctx, pzg::launch_adler32_many(base, off, len, out, n, sh.num_cus, sh.stream));
-        HIP_TRY(ctx, hipEventRecord(sh.ev1, sh.stream));
-        sh.timed = true;
-        sh.last_was_host = false;
-        if (!(flags & PZG_ASYNC)) HIP_TRY(ctx, hipStreamSynchronize(sh.stream));
-        return PZG_RC_OK;
+        return stream_launch(ctx, sh, flags, nothing_before, [&](hipStream_t s) { return pzg::launch_adler32_many(base, off, len, out, n, sh.num_cus, s); });
     });
 }
 
