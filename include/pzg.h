@@ -614,6 +614,73 @@ PZG_API int pzg_expand_many(pzg_ctx *ctx,
         uint32_t n, uint32_t flags);         /* 0, PZG_DEVICE_PTRS, PZG_DEVICE_PTRS | PZG_ASYNC */
 
 /*
+ * pzg_unpredict_many (0.5): EXTENSION -- TIFF horizontal differencing undone (TIFF 6.0 section 14, Predictor 2; the PDF FlateDecode
+ * Predictor 2 is the same) and strips or tiles clipped to a window, the second half of reading a Deflate-compressed TIFF: all n
+ * jobs in one launch, the rows of a job spread over several wavefronts.  One job is one strip or tile as it was decoded; nothing in
+ * the call knows of TIFF's tags.
+ *   desc[i]     one job (pzg_unpredict_desc below; its reserved words are 0):
+ *     source      `rows` stored rows of src_row_bytes bytes, dense, at src_base + src_off, at any alignment.  For a tile
+ *                 src_row_bytes is TileWidth x samples x sample_bytes, padding included, and rows is TileLength; for a strip, rows
+ *                 is what that strip really has.
+ *     window      what is delivered: the rows [win_row, win_row + win_rows) of the job and, of each, the bytes [win_byte,
+ *                 win_byte + win_bytes) of the RECONSTRUCTED row.  Clipping a tile at the image's edge is win_row = win_byte = 0
+ *                 with the image's remainder as sizes; a region read clips on all four sides.  The recurrence always starts at
+ *                 byte 0 of the stored row, whatever the window.
+ *     delivery    window row r at dst_base + dst_off + r * dst_stride (dst_stride >= win_bytes).  The bytes between win_bytes and
+ *                 the stride and everything outside the extents are untouched.  The dst extents overlap neither each other nor src.
+ *     predictor   1: a clipped copy.  2: horizontal differencing -- sample k of a row is stored[k] + actual[k - samples] modulo
+ *                 2^(8 x sample_bytes), taken in the file's byte order (big_endian != 0: most significant byte first) and delivered
+ *                 in the file's byte order: nothing is swapped in the output.
+ *     samples     1 .. 4: the stride of the recurrence in samples -- SamplesPerPixel for chunky data, 1 for a separate plane.
+ *                 sample_bytes: 1, 2, 4 or 8.  (Both are held to their lists with predictor 1 as well, where nothing else is made
+ *                 of them.)
+ *   src_len[i]  the bytes of job i that src holds: a separate array so that it can be the out_len array a preceding
+ *               pzg_decompress_many(... PZG_ASYNC) wrote.
+ *   status[i]   PZG_OK
+ *               PZG_E_TRUNCATED  src_len[i] < rows * src_row_bytes: d0 is the number of stored rows that lie wholly inside
+ *                                src_len[i]; those of them that fall in the window are delivered.
+ *               rows, src_row_bytes, win_rows or win_bytes of 0: PZG_OK, nothing read or written.
+ *   detail      2n words (d0, d1 per job), or NULL: 0, 0 of a PZG_OK job.
+ * flags: as for pzg_expand_many.  0 -- every pointer is host memory: the call stages the spans of src that the jobs name, desc,
+ * src_len and dst's extents through the context's arenas and returns when dst and status are filled; PZG_DEVICE_PTRS -- every
+ * pointer is device memory, the launch goes on the context's stream (pzg_set_stream) in call order, and with PZG_ASYNC as well the
+ * call only enqueues: pzg_decompress_many, pzg_unpredict_many and pzg_sync chain without a host round trip.  pzg_last_kernel_ms
+ * reports the launch.
+ * PZG_RC_BAD_ARG: n == 0, any other flag, a null array, a context of several devices; with host pointers also, of a job that is not
+ * empty, a predictor other than 1 and 2, a sample_bytes or samples outside the lists, a src_row_bytes that is no multiple of
+ * samples x sample_bytes with predictor 2, a window that reaches outside the stored job and a dst_stride below win_bytes.  Device
+ * arrays are not read by the host: there such a job gets PZG_E_FILTER with d0 = 0xffffffff and
+ * d1 = predictor << 16 | sample_bytes << 8 | samples, and nothing of it is read or written.
+ * Offsets and strides are 64-bit.  Nothing is read but the aligned dwords that hold bytes of
+ * src_off .. + min(src_len[i], rows * src_row_bytes).
+ */
+typedef struct pzg_unpredict_desc {
+    uint64_t src_off;                  /*  0 */
+    uint64_t dst_off, dst_stride;      /*  8, 16 */
+    uint32_t src_row_bytes, rows;      /* 24, 28 */
+    uint32_t win_row, win_rows;        /* 32, 36 */
+    uint32_t win_byte, win_bytes;      /* 40, 44 */
+    uint8_t predictor, sample_bytes;   /* 48, 49 */
+    uint8_t samples, big_endian;       /* 50, 51 */
+    uint32_t reserved[3];              /* 52: 0 */
+} pzg_unpredict_desc;
+#if defined(__cplusplus)
+static_assert(sizeof(pzg_unpredict_desc) == 64 && offsetof(pzg_unpredict_desc, dst_off) == 8 && offsetof(pzg_unpredict_desc, src_row_bytes) == 24 &&
+              offsetof(pzg_unpredict_desc, win_row) == 32 && offsetof(pzg_unpredict_desc, win_byte) == 40 && offsetof(pzg_unpredict_desc, predictor) == 48 &&
+              offsetof(pzg_unpredict_desc, big_endian) == 51 && offsetof(pzg_unpredict_desc, reserved) == 52, "pzg_unpredict_desc is 64 bytes, laid out as commented");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(pzg_unpredict_desc) == 64 && offsetof(pzg_unpredict_desc, src_row_bytes) == 24 && offsetof(pzg_unpredict_desc, predictor) == 48,
+               "pzg_unpredict_desc is 64 bytes, laid out as commented");
+#endif
+
+PZG_API int pzg_unpredict_many(pzg_ctx *ctx,
+        const uint8_t *src_base, const uint64_t *src_len,   /* n */
+        uint8_t *dst_base,
+        const pzg_unpredict_desc *desc,      /* n */
+        int32_t *status, uint32_t *detail,   /* detail: 2n, or NULL */
+        uint32_t n, uint32_t flags);         /* 0, PZG_DEVICE_PTRS, PZG_DEVICE_PTRS | PZG_ASYNC */
+
+/*
  * decompressIncremental / ZlibDecoder (Zlib.hs:3-8, Monad.hs:163-197; driver Deflate.hs:30-48), batched: a pzg_decoder
  * is n suspended zlib decoders (gzip or raw ones: pzg_decoder_create_format) living on the device (a one-device context).  pzg_decoder_feed continues the decoders
  * idx[0..m) (idx = NULL: all n, m ignored) -- one launch, one wavefront per decoder -- as far as their input and

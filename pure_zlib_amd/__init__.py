@@ -13,7 +13,9 @@ Only what the hot path needs lives here:
   png.py     PNG images in batches: one decode launch, one unfilter launch (pzg_unfilter_many), the pixels in one copy;
              Adam7 images with adam7=True, deinterlaced on the device (pzg_adam7_many); expand="rgba8" | "rgb8": (H, W, 4 | 3) uint8 pixels
              of every colour type, expanded on the device (pzg_expand_many); read_png_batch: one (N, H, W, C) tensor
-  cxx/       the same module mirror in C++ (header-only)
+  tiff.py    Deflate-compressed TIFF files in batches: every strip and tile of every page of every file in one decode launch, Predictor 2
+             undone and tiles clipped in one more (pzg_unpredict_many); read_tiff_region decodes only what covers a rectangle
+  cxx/       the same module mirror in C++ (header-only; the image stages are not mirrored)
 
 There is no CPU fallback: importing works anywhere, computing needs libpzg.so and a gfx950 device.
 """
@@ -25,4 +27,5 @@ from .zlib import (  # noqa: F401
 )
 from .indexed import Index, adler32_combine, crc32_combine  # noqa: F401
 from .gzfile import MemberIndex, decompress_gzip_file  # noqa: F401
+from .tiff import TiffImage, TiffPage, parse_tiff, read_tiff, read_tiff_many, read_tiff_region, test_tiff_many  # noqa: F401
 from .incremental import FORMATS, DecoderPool, decompress_incremental, decompressIncremental  # noqa: F401

@@ -49,6 +49,7 @@
 #include "scan_core.h"  // (ScanStream, ScanResult: the tables of pzg_index_scan_many)
 #include "pzg_unfilter_kernel.h"  // (unfilter_kernel and its launcher; unfilter_core.h: its statuses, and what it takes for a legal bpp)
 #include "pzg_expand_kernel.h"    // (expand_kernel and its launcher; expand_core.h: its statuses, a legal geometry, the bytes of a row)
+#include "pzg_unpredict_kernel.h" // (unpredict_kernel and its launcher; unpredict_core.h: its statuses, a legal geometry, the rows inside src_len)
 #include "pzg_adam7_kernel.h"     // (adam7_kernel and its launcher; adam7_core.h: its statuses, a legal geometry, an image's source extent)
 
 namespace {
@@ -1155,15 +1156,16 @@ int stream_launch(pzg_ctx *ctx, Shard &sh, uint32_t flags, Before &&before, Laun
 }
 inline int nothing_before() { return PZG_RC_OK; }
 
-// ---- the image stages (pzg_unfilter_many, pzg_adam7_many, pzg_expand_many).  What all three take: one device, PZG_DEVICE_PTRS, PZG_ASYNC with it
+// ---- the image stages (pzg_unfilter_many, pzg_adam7_many, pzg_expand_many, pzg_unpredict_many).  What all of them take: one device, PZG_DEVICE_PTRS, PZG_ASYNC with it
 inline bool stage_call_ok(const pzg_ctx *ctx, uint32_t n, uint32_t flags)
 {
     return ctx_live(ctx) && n != 0 && !(flags & ~(PZG_DEVICE_PTRS | PZG_ASYNC)) && (!(flags & PZG_ASYNC) || (flags & PZG_DEVICE_PTRS)) && ctx->shards.size() == 1;
 }
 
 // the rows of an image the kernel delivered (image_stage_host): those in front of a failure, or all or none
-inline uint32_t rows_before_failure(int32_t status, uint32_t detail0, uint32_t rows) { return status == PZG_OK ? rows : detail0; }
-inline uint32_t rows_all_or_none(int32_t status, uint32_t, uint32_t rows) { return status == PZG_OK ? rows : 0u; }
+// (i: the image's index, for a stage whose rule needs more of the image than its rows)
+inline uint32_t rows_before_failure(int32_t status, uint32_t detail0, uint32_t rows, uint32_t) { return status == PZG_OK ? rows : detail0; }
+inline uint32_t rows_all_or_none(int32_t status, uint32_t, uint32_t rows, uint32_t) { return status == PZG_OK ? rows : 0u; }
 
 // The host-pointer form of an image stage, on lane 0.  The spans of src and dst that the images cover (pzg_stage_span.h) travel
 // through the lane's arenas, each at its place modulo 16; with them the metadata block: `meta` -- what the stage took for its own
@@ -1218,7 +1220,7 @@ int image_stage_host(pzg_ctx *ctx, const char *name, uint32_t n, const uint8_t *
         if (detail) memcpy(detail, h_detail, 8 * (size_t)n);
         for (uint32_t i = 0; i < n; ++i) {
             const pzg::StageExtent e = extent(i);
-            sp.copy_back(e, delivered(h_status[i], h_detail[2 * (size_t)i], e.rows), ln.h_out[0].p, dst_base);
+            sp.copy_back(e, delivered(h_status[i], h_detail[2 * (size_t)i], e.rows, i), ln.h_out[0].p, dst_base);
         }
         return PZG_RC_OK;
     });
@@ -1875,7 +1877,7 @@ int pzg_gzip_layout(pzg_ctx *ctx, const uint8_t *in, uint64_t in_len, const uint
     });
 }
 
-// The three image stages: the device-pointer form is one stream_launch, the host-pointer form image_stage_host.
+// The image stages: the device-pointer form is one stream_launch, the host-pointer form image_stage_host.
 // Scanline unfiltering (unfilter_core.h).  An image whose src_len is 0 reads nothing: its src_off does not count for the span.  Of an
 // image that fails the rows in front of the failure are delivered.
 int pzg_unfilter_many(pzg_ctx *ctx, const uint8_t *src_base, const uint64_t *src_off, const uint64_t *src_len, uint8_t *dst_base, const uint64_t *dst_off,
@@ -2037,6 +2039,58 @@ int pzg_expand_many(pzg_ctx *ctx, const uint8_t *src_base, uint8_t *dst_base, co
             a.scratch = m_scratch.in(dm);
         },
         pzg::launch_expand, rows_all_or_none);
+}
+
+// TIFF Predictor 2 and window clipping (unpredict_core.h).  The descriptors travel with their offsets counted from the spans' starts.
+// Of a job that is truncated the window's rows that lie wholly inside src_len are delivered.
+int pzg_unpredict_many(pzg_ctx *ctx, const uint8_t *src_base, const uint64_t *src_len, uint8_t *dst_base, const pzg_unpredict_desc *desc, int32_t *status,
+                       uint32_t *detail, uint32_t n, uint32_t flags)
+{
+    using U = pzg::Unpredict;
+    static_assert(U::ST_FILTER == PZG_E_FILTER && U::ST_TRUNCATED == PZG_E_TRUNCATED && U::ST_OK == PZG_OK, "the core's statuses are the header's");
+    static_assert(sizeof(U::Desc) == sizeof(pzg_unpredict_desc) && offsetof(U::Desc, dst_off) == offsetof(pzg_unpredict_desc, dst_off) &&
+                      offsetof(U::Desc, dst_stride) == offsetof(pzg_unpredict_desc, dst_stride) &&
+                      offsetof(U::Desc, src_row_bytes) == offsetof(pzg_unpredict_desc, src_row_bytes) && offsetof(U::Desc, rows) == offsetof(pzg_unpredict_desc, rows) &&
+                      offsetof(U::Desc, win_row) == offsetof(pzg_unpredict_desc, win_row) && offsetof(U::Desc, win_rows) == offsetof(pzg_unpredict_desc, win_rows) &&
+                      offsetof(U::Desc, win_byte) == offsetof(pzg_unpredict_desc, win_byte) && offsetof(U::Desc, win_bytes) == offsetof(pzg_unpredict_desc, win_bytes) &&
+                      offsetof(U::Desc, predictor) == offsetof(pzg_unpredict_desc, predictor) &&
+                      offsetof(U::Desc, sample_bytes) == offsetof(pzg_unpredict_desc, sample_bytes) && offsetof(U::Desc, samples) == offsetof(pzg_unpredict_desc, samples) &&
+                      offsetof(U::Desc, big_endian) == offsetof(pzg_unpredict_desc, big_endian) && offsetof(U::Desc, reserved) == offsetof(pzg_unpredict_desc, reserved),
+                  "the core's descriptor is the header's");
+    if (!stage_call_ok(ctx, n, flags) || !src_base || !src_len || !dst_base || !desc || !status) return PZG_RC_BAD_ARG;
+    if (flags & PZG_DEVICE_PTRS)
+        return guarded(ctx, "pzg_unpredict_many", [&]() -> int {
+            const pzg::UnpredictArgs a{src_base, src_len, dst_base, desc, status, detail, n};
+            return stream_launch(ctx, *ctx->shards[0], flags, nothing_before, [&](hipStream_t s) { return pzg::launch_unpredict(a, s); });
+        });
+    // host pointers: what the device form leaves to the kernel
+    const U::Desc *hd = (const U::Desc *)(const void *)desc;
+    for (uint32_t i = 0; i < n; ++i)
+        if (!U::empty(hd[i]) && !U::geometry_ok(hd[i])) return PZG_RC_BAD_ARG;
+    pzg::MetaCursor c;
+    const auto m_desc = c.take<U::Desc>(n);
+    const auto m_slen = c.take<uint64_t>(n);
+    const auto extent = [&](uint32_t i) {
+        const U::Desc &D = hd[i];
+        if (U::empty(D)) return pzg::StageExtent{};
+        return pzg::StageExtent{D.src_off, std::min(src_len[i], (uint64_t)D.rows * D.src_row_bytes), D.dst_off, D.dst_stride, D.win_bytes, D.win_rows, false};
+    };
+    return image_stage_host(
+        ctx, "pzg_unpredict_many", n, src_base, dst_base, status, detail, c, extent,
+        [&](uint8_t *hm, uint8_t *dm, const pzg::StageSpans &sp, pzg::UnpredictArgs &a) {
+            U::Desc *sd = m_desc.in(hm);
+            for (uint32_t i = 0; i < n; ++i) {
+                sd[i] = hd[i];
+                sd[i].src_off = sp.src_at(extent(i));
+                sd[i].dst_off = sp.dst_at(extent(i));
+            }
+            memcpy(m_slen.in(hm), src_len, 8 * (size_t)n);
+            a.desc = m_desc.in(dm);
+            a.src_len = m_slen.in(dm);
+        },
+        pzg::launch_unpredict,
+        // the window's rows in front of the first stored row that does not lie wholly inside src_len
+        [&](int32_t st, uint32_t d0, uint32_t rows, uint32_t i) { return st == PZG_OK ? rows : st == PZG_E_TRUNCATED && d0 > hd[i].win_row ? d0 - hd[i].win_row : 0u; });
 }
 
 int pzg_decompress_many_sharded(pzg_ctx *ctx, const pzg_device_batch *batches, uint32_t nbatches, uint32_t flags)
