@@ -39,7 +39,8 @@ from typing import List, Optional, Sequence, Tuple, Union
 import numpy as np
 
 from . import _ffi
-from .zlib import EXPAND_DESC, Context, DecompressionError, PinnedArena, default_context, error_from_status
+from ._batch import DeviceChain, load, pack
+from .zlib import EXPAND_DESC, Context, DecompressionError, default_context, error_from_status
 
 SIGNATURE = b"\x89PNG\r\n\x1a\n"
 _CHANNELS = {0: 1, 2: 3, 3: 1, 4: 2, 6: 4}
@@ -174,11 +175,185 @@ def _shape(img: PngImage, flat: np.ndarray) -> np.ndarray:
     return flat.reshape(img.height, img.row_bytes)
 
 
-def _load(src) -> Tuple[Optional[str], bytes]:
-    if isinstance(src, (bytes, bytearray, memoryview)):
-        return None, bytes(src)
-    with open(src, "rb") as f:
-        return os.fspath(src), f.read()
+def _collect(sources, adam7: bool, expand: Optional[str]):
+    """Loads and parses.  (names, results with the exception of every source that cannot be read and None elsewhere, good =
+    [(index, image, stream)], laced = [(place in good, its passes)] of the interlaced ones)."""
+    results: List[Union[PngImage, Exception, None]] = [None] * len(sources)
+    names, good, laced = [], [], []
+    for k, src in enumerate(sources):
+        name = "#%d" % k
+        try:
+            path, blob = load(src)
+            name = path or name
+            img, z, lace = _parse(name, blob, adam7, expand is not None)
+            if lace:
+                laced.append((len(good), _passes(img)))
+            good.append((k, img, z))
+        except (ValueError, NotImplementedError, OSError) as e:
+            results[k] = e
+        names.append(name)
+    return names, results, good, laced
+
+
+@dataclass
+class _Layout:
+    """Where everything of a batch lies, an entry per good image: dec_cap, the exact decoded size; the file's rows, which the
+    unfilter and Adam7 launches deliver at (file_off, file_stride) -- into the pixel buffer, or with `expand` dense into a scratch of
+    file_total bytes that the expansion reads; the pixels, pix bytes at (pix_off, pix_stride) of a buffer of pix_total bytes, or
+    where device_out says (pix_total is None then).  Offsets, strides, dec_cap and pix are u64."""
+    dec_cap: np.ndarray
+    row_bytes: np.ndarray  # u32
+    height: np.ndarray     # u32
+    bpp: np.ndarray        # u8
+    file_off: np.ndarray
+    file_stride: np.ndarray
+    file_total: Optional[int]
+    pix_off: np.ndarray
+    pix_stride: np.ndarray
+    pix: np.ndarray
+    pix_total: Optional[int]
+
+
+def _layout(good, laced, expand: Optional[str], device_out) -> _Layout:
+    images = [i for _k, i, _z in good]
+    row_bytes = np.array([i.row_bytes for i in images], dtype=np.uint32)
+    height = np.array([i.height for i in images], dtype=np.uint32)
+    rows, file_rb = height.astype(np.uint64), row_bytes.astype(np.uint64)
+    dec_cap = rows * (file_rb + np.uint64(1))
+    for j, passes in laced:  # the seven reduced images, each row with its filter byte
+        dec_cap[j] = sum(ph * (1 + prb) for _p, ph, prb in passes)
+    out_rb = file_rb if expand is None else np.array([i.width * _EXPAND[expand][1] for i in images], dtype=np.uint64)
+    if device_out is not None:
+        pix_off = np.array([device_out[1][k] for k, _i, _z in good], dtype=np.uint64)
+        pix_stride, pix_total = np.array([device_out[2][k] for k, _i, _z in good], dtype=np.uint64), None
+        if (pix_stride < out_rb).any():
+            raise ValueError("device_out: a stride below the image's row_bytes")
+    else:
+        (pix_off, pix_total), pix_stride = pack(rows * out_rb), out_rb
+    if expand is None:
+        file_off, file_stride, file_total = pix_off, pix_stride, None
+    else:
+        (file_off, file_total), file_stride = pack(rows * file_rb), file_rb
+    return _Layout(dec_cap, row_bytes, height, np.array([i.bpp for i in images], dtype=np.uint8), file_off, file_stride, file_total,
+                   pix_off, pix_stride, rows * out_rb, pix_total)
+
+
+_PASS_JOB = np.dtype([("src_off", "<u8"), ("src_len", "<u8"), ("dst_off", "<u8"), ("row_bytes", "<u4"), ("height", "<u4"), ("bpp", "u1")])
+_WEAVE = np.dtype([("src_off", "<u8"), ("dst_off", "<u8"), ("dst_stride", "<u8"), ("width", "<u4"), ("height", "<u4"), ("pixel_bits", "u1")])
+
+
+def _pass_jobs(good, laced, lay: _Layout, dec_off) -> Tuple[np.ndarray, np.ndarray, int]:
+    """(_PASS_JOB[m], _WEAVE[len(laced)], the bytes of the scratch between them).  Every pass that has pixels is one unfilter job,
+    from its place in the image's decoded stream (dec_off) dense into the scratch; a weave job puts an image's passes into its rows."""
+    scr_off, scr_total = pack([sum(ph * prb for _p, ph, prb in passes) for _j, passes in laced])
+    jobs = []
+    for (j, passes), d_at in zip(laced, scr_off.tolist()):
+        s_at = int(dec_off[j])
+        for _p, ph, prb in passes:
+            jobs.append((s_at, ph * (1 + prb), d_at, prb, ph, int(lay.bpp[j])))
+            s_at += ph * (1 + prb)
+            d_at += ph * prb
+    weave = [(scr_off[i], lay.file_off[j], lay.file_stride[j], good[j][1].width, good[j][1].height, good[j][1].channels * good[j][1].bit_depth)
+             for i, (j, _ps) in enumerate(laced)]
+    return np.array(jobs, dtype=_PASS_JOB), np.array(weave, dtype=_WEAVE), scr_total
+
+
+def _run(ctx: Context, good, laced, lay: _Layout, expand: Optional[str], out_ptr: Optional[int]):
+    """The launches.  Returns (out_len, {launch: (status, detail)}, the pixel buffer on the host or None, bad_index)."""
+    n, plain = len(good), len(laced) < len(good)  # (a batch of interlaced images only has nothing for the first unfilter launch)
+    with DeviceChain(ctx, [(z, 0, len(z)) for _k, _i, z in good], lay.dec_cap) as ch:
+        pix = ch.scratch(lay.pix_total) if out_ptr is None else None
+        pix_ptr = out_ptr if pix is None else pix.data_ptr()
+        rows = ch.scratch(lay.file_total) if expand is not None else None
+        rows_ptr = pix_ptr if rows is None else rows.data_ptr()
+        if plain:
+            height = lay.height.copy()
+            height[[j for j, _ps in laced]] = 0  # (no rows: this launch neither reads nor writes an interlaced image)
+            u_dst_off, u_stride, u_row_bytes, u_height, u_bpp = (ch.upload(a) for a in (lay.file_off, lay.file_stride, lay.row_bytes, height, lay.bpp))
+            u_status, u_detail = ch.results("unfilter", n)
+        if laced:
+            jobs, weave, scr_total = _pass_jobs(good, laced, lay, ch.dec_off)
+            scr_ptr = ch.scratch(scr_total).data_ptr()
+            j_src_off, j_src_len, j_dst_off, j_stride, j_row_bytes, j_height, j_bpp = (ch.upload(a) for a in (
+                jobs["src_off"], jobs["src_len"], jobs["dst_off"], jobs["row_bytes"].astype(np.uint64), jobs["row_bytes"], jobs["height"], jobs["bpp"]))
+            w_src_off, w_dst_off, w_stride, w_width, w_height, w_bits = (ch.upload(weave[f]) for f in _WEAVE.names)
+            j_status, j_detail = ch.results("passes", len(jobs))
+            w_status, _no_detail = ch.results("adam7", len(weave))
+        if expand is not None:
+            desc, pal = _expand_descriptors([i for _k, i, _z in good], lay.file_off, lay.file_stride, lay.pix_off, lay.pix_stride, _EXPAND[expand][0])
+            x_desc, x_pal = ch.upload(desc), ch.upload(pal)
+            x_status, x_detail = ch.results("expand", n)
+        ch.decode()
+        if plain:
+            ctx.unfilter_many_device(ch.dec_ptr, ch.dec_off_ptr, ch.out_len_ptr, rows_ptr, u_dst_off, u_stride, u_row_bytes, u_height, u_bpp, u_status,
+                                     u_detail, n, sync=False)
+        if laced:
+            ctx.unfilter_many_device(ch.dec_ptr, j_src_off, j_src_len, scr_ptr, j_dst_off, j_stride, j_row_bytes, j_height, j_bpp, j_status, j_detail,
+                                     len(jobs), sync=False)
+            ctx.adam7_many_device(scr_ptr, w_src_off, rows_ptr, w_dst_off, w_stride, w_width, w_height, w_bits, w_status, 0, len(weave), sync=False)
+        if expand is not None:
+            ctx.expand_many_device(rows_ptr, pix_ptr, x_pal, x_desc, x_status, x_detail, n, sync=False)
+        blocks = ch.finish()
+        bad_index = _bad_indices(good, lay, blocks["expand"], rows) if expand is not None else {}
+        return ch.out_len(), blocks, pix.cpu().numpy() if pix is not None else None, bad_index  # (the pixels: the one copy out)
+
+
+def _bad_indices(good, lay: _Layout, expansion, rows) -> dict:
+    """{place in good: (row, x, the index found there) of an image the expansion refused; () where it refused for another reason}"""
+    out, (xstatus, xdetail) = {}, expansion
+    for j in np.flatnonzero(xstatus != _ffi.OK):
+        row, x, depth = int(xdetail[j, 0]), int(xdetail[j, 1]), good[j][1].bit_depth
+        if int(xstatus[j]) != _ffi.E_PALETTE:
+            out[int(j)] = ()
+            continue
+        byte = int(rows[int(lay.file_off[j]) + row * int(lay.file_stride[j]) + x * depth // 8])  # (one byte back: the index itself)
+        out[int(j)] = (row, x, (byte >> (8 - depth - x * depth % 8)) & ((1 << depth) - 1))
+    return out
+
+
+def _pass_errors(laced, blocks) -> dict:
+    """{place in good: (pass or 0 for the deinterlacing, status, detail 0, detail 1)}: what an image's passes and its
+    deinterlacing say, the first pass in pass order first."""
+    if not laced:
+        return {}
+    out, at, (jstatus, jdetail), (astatus, _none) = {}, 0, blocks["passes"], blocks["adam7"]
+    for i, (j, passes) in enumerate(laced):
+        for t, (pno, _ph, _prb) in enumerate(passes):
+            if j not in out and int(jstatus[at + t]) != _ffi.OK:
+                out[j] = (pno, int(jstatus[at + t]), int(jdetail[at + t, 0]), int(jdetail[at + t, 1]))
+        if j not in out and int(astatus[i]) != _ffi.OK:
+            out[j] = (0, int(astatus[i]), 0, 0)
+        at += len(passes)
+    return out
+
+
+def _verdict(name: str, img: PngImage, z: bytes, decode, unfilter, pass_error, bad_index, out_len: int, dec_cap: int) -> Optional[Exception]:
+    """The error of one image, or None: the first of what the decode, the passes, the unfilter and the expansion say.  decode,
+    unfilter: (status, its detail pair); pass_error: an entry of _pass_errors or None; bad_index: one of _bad_indices or None."""
+    (st, detail), (ust, (row, ft)) = decode, unfilter
+    if st == _ffi.E_OUT_TOO_SMALL:
+        return _format_error("%s: too much image data" % name)
+    if st != _ffi.OK:
+        e = error_from_status(z, st, detail)
+        return DecompressionError(e.constructor, "%s: %s" % (name, e.message), e.status, e.detail)
+    if out_len != dec_cap:
+        return _format_error("%s: not enough image data" % name)
+    if pass_error is not None:
+        pno, pst, d0, d1 = pass_error
+        if pno and pst == _ffi.E_FILTER:
+            return DecompressionError("FormatError", "%s: pass %d: row %d has filter type %d" % (name, pno, d0, d1), pst, (d0, d1))
+        return _format_error("%s: the image's passes could not be put together" % name)
+    if ust == _ffi.E_FILTER:
+        return DecompressionError("FormatError", "%s: row %d has filter type %d" % (name, int(row), int(ft)), ust, (int(row), int(ft)))
+    if ust != _ffi.OK:
+        return _format_error("%s: not enough image data" % name)
+    if bad_index is not None:
+        if not bad_index:
+            return _format_error("%s: the image's pixels could not be expanded" % name)
+        row, x, index = bad_index
+        return DecompressionError("FormatError", "%s: row %d, pixel %d: palette index %d of %d" % (name, row, x, index, len(img.palette) // 3),
+                                  _ffi.E_PALETTE, (row, x))
+    return None
 
 
 def read_png_many(blobs_or_paths: Sequence[Union[str, os.PathLike, bytes, bytearray, memoryview]], ctx: Optional[Context] = None,
@@ -190,182 +365,21 @@ def read_png_many(blobs_or_paths: Sequence[Union[str, os.PathLike, bytes, bytear
     images are read too, deinterlaced on the device (without it each is NotImplementedError).  expand = "rgba8" | "rgb8": `data` is
     (H, W, 4 | 3) uint8 pixels for every colour type, expanded on the device (the module's docstring has the rules), and device_out's
     offsets and strides describe those rows; an image with an error may leave anything in its own rows there."""
-    import torch
     if expand is not None and expand not in _EXPAND:
         raise ValueError("expand: None, 'rgba8' or 'rgb8', not %r" % (expand,))
-    results: List[Union[PngImage, Exception, None]] = [None] * len(blobs_or_paths)
-    names, good, laced = [], [], []  # good: (index, image, stream); laced: the interlaced ones, as (place in good, its passes)
-    for k, src in enumerate(blobs_or_paths):
-        name = "#%d" % k
-        try:
-            path, blob = _load(src)
-            name = path or name
-            img, z, lace = _parse(name, blob, adam7, expand is not None)
-            if lace:
-                laced.append((len(good), _passes(img)))
-            good.append((k, img, z))
-        except (ValueError, NotImplementedError, OSError) as e:
-            results[k] = e
-        names.append(name)
+    names, results, good, laced = _collect(blobs_or_paths, adam7, expand)
     if not good:
         return results
-    n = len(good)
-    pad = lambda a: (a + np.uint64(15)) & ~np.uint64(15)  # noqa: E731  (16-byte aligned extents: the wide store path)
-    in_len = np.array([len(z) for _k, _i, z in good], dtype=np.uint64)
-    row_bytes = np.array([i.row_bytes for _k, i, _z in good], dtype=np.uint32)
-    height = np.array([i.height for _k, i, _z in good], dtype=np.uint32)
-    bpp = np.array([i.bpp for _k, i, _z in good], dtype=np.uint8)
-    dec_cap = height.astype(np.uint64) * (row_bytes.astype(np.uint64) + np.uint64(1))
-    for j, passes in laced:  # the seven reduced images, each row with its filter byte
-        dec_cap[j] = sum(ph * (1 + prb) for _p, ph, prb in passes)
-    pix = height.astype(np.uint64) * row_bytes.astype(np.uint64)
-    in_off, dec_off, pix_off = (np.zeros(n, dtype=np.uint64) for _ in range(3))
-    in_off[1:] = np.cumsum(pad(in_len))[:-1]
-    dec_off[1:] = np.cumsum(pad(dec_cap + np.uint64(4)))[:-1]  # (4: a stream that decodes to MORE than its capacity claims no neighbour's dword)
-    pix_off[1:] = np.cumsum(pad(pix))[:-1]
-    stride = row_bytes.astype(np.uint64)
-    if expand is not None:
-        # the unfilter and Adam7 launches deliver the file's rows dense into a scratch (file_off, file_stride); pix, pix_off and
-        # stride become those of the expanded rows, which the expansion writes
-        file_off, file_stride, tot_file = pix_off, stride, int(pix_off[-1] + pad(pix)[-1]) + 16
-        out_rb = np.array([i.width * _EXPAND[expand][1] for _k, i, _z in good], dtype=np.uint64)
-        pix = height.astype(np.uint64) * out_rb
-        pix_off = np.zeros(n, dtype=np.uint64)
-        pix_off[1:] = np.cumsum(pad(pix))[:-1]
-        stride = out_rb
-    if device_out is not None:
-        out_ptr = int(device_out[0])
-        pix_off = np.array([device_out[1][k] for k, _i, _z in good], dtype=np.uint64)
-        stride = np.array([device_out[2][k] for k, _i, _z in good], dtype=np.uint64)
-        if (stride < (row_bytes if expand is None else out_rb)).any():
-            raise ValueError("device_out: a stride below the image's row_bytes")
-    if expand is None:
-        file_off, file_stride = pix_off, stride
-    tot_in = int(in_off[-1] + pad(in_len)[-1]) + 16
-    tot_dec = int(dec_off[-1] + pad(dec_cap + np.uint64(4))[-1]) + 16
-    tot_pix = int(pix_off[-1] + pad(pix)[-1]) + 16
-    ctx = ctx or default_context()
-    dev = torch.device("cuda", ctx.device)
-    ain = PinnedArena(tot_in)
-    try:
-        for j, (_k, _i, z) in enumerate(good):
-            ain.a[int(in_off[j]):int(in_off[j]) + len(z)] = np.frombuffer(z, dtype=np.uint8)
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8)).to(dev)  # noqa: E731
-        d_in = up(ain.a[:tot_in])
-        plain_height = height.copy()
-        for j, _ps in laced:
-            plain_height[j] = 0  # (no rows: the first unfilter launch neither reads nor writes an interlaced image)
-        d_meta = [up(a) for a in (in_off, in_len, dec_off, dec_cap, file_off, file_stride, row_bytes, plain_height, bpp)]
-        d_dec = torch.empty(tot_dec, dtype=torch.uint8, device=dev)
-        d_pix = torch.empty(tot_pix, dtype=torch.uint8, device=dev) if device_out is None else None
-        d_out_len = torch.zeros(8 * n, dtype=torch.uint8, device=dev)
-        d_status = torch.zeros(2 * 4 * n, dtype=torch.uint8, device=dev)   # the decode's, the unfilter's
-        d_detail = torch.zeros(2 * 8 * n, dtype=torch.uint8, device=dev)
-        if laced:
-            # every pass that has pixels is one unfilter job, from its place in the image's decoded stream into a scratch of dense
-            # passes; then one launch weaves each image's passes into its rows
-            jobs, scr_off, scr_at = [], [], 0  # jobs: (src_off, src_len, dst_off, row bytes, rows, bpp)
-            for j, passes in laced:
-                scr_off.append(scr_at)
-                s_at = int(dec_off[j])
-                for _p, ph, prb in passes:
-                    jobs.append((s_at, ph * (1 + prb), scr_at, prb, ph, int(bpp[j])))
-                    s_at += ph * (1 + prb)
-                    scr_at += ph * prb
-                scr_at = (scr_at + 15) & ~15
-            m, jj = len(jobs), [j for j, _ps in laced]
-            col = lambda c, t: np.array([job[c] for job in jobs], dtype=t)  # noqa: E731
-            d_jobs = [up(a) for a in (col(0, np.uint64), col(1, np.uint64), col(2, np.uint64), col(3, np.uint64), col(3, np.uint32), col(4, np.uint32),
-                                      col(5, np.uint8), np.array(scr_off, dtype=np.uint64), file_off[jj], file_stride[jj],
-                                      np.array([good[j][1].width for j in jj], dtype=np.uint32), height[jj],
-                                      np.array([good[j][1].channels * good[j][1].bit_depth for j in jj], dtype=np.uint8))]
-            d_scr = torch.empty(scr_at + 16, dtype=torch.uint8, device=dev)
-            d_jstatus = torch.zeros(4 * m, dtype=torch.uint8, device=dev)   # the pass jobs'
-            d_jdetail = torch.zeros(8 * m, dtype=torch.uint8, device=dev)
-            d_astatus = torch.zeros(4 * len(jj), dtype=torch.uint8, device=dev)  # the deinterlacing's
-        if expand is not None:
-            desc, pal = _expand_descriptors([i for _k, i, _z in good], file_off, file_stride, pix_off, stride, _EXPAND[expand][0])
-            d_file = torch.empty(tot_file, dtype=torch.uint8, device=dev)
-            d_desc, d_pal = up(desc), up(pal)
-            d_xstatus = torch.zeros(4 * n, dtype=torch.uint8, device=dev)  # the expansion's
-            d_xdetail = torch.zeros(8 * n, dtype=torch.uint8, device=dev)
-        torch.cuda.synchronize(dev)
-        p = [t.data_ptr() for t in d_meta]
-        ctx.decompress_many_device(d_in.data_ptr(), p[0], p[1], d_dec.data_ptr(), p[2], p[3], d_out_len.data_ptr(), d_status.data_ptr(),
-                                   d_detail.data_ptr(), 0, 0, n, sync=False)
-        pix_ptr = out_ptr if device_out is not None else d_pix.data_ptr()
-        file_ptr = pix_ptr if expand is None else d_file.data_ptr()
-        if len(laced) < n:  # (a batch of interlaced images only has nothing for this launch)
-            ctx.unfilter_many_device(d_dec.data_ptr(), p[2], d_out_len.data_ptr(), file_ptr, p[4], p[5], p[6], p[7], p[8], d_status.data_ptr() + 4 * n,
-                                     d_detail.data_ptr() + 8 * n, n, sync=False)
-        if laced:
-            q = [t.data_ptr() for t in d_jobs]
-            ctx.unfilter_many_device(d_dec.data_ptr(), q[0], q[1], d_scr.data_ptr(), q[2], q[3], q[4], q[5], q[6], d_jstatus.data_ptr(),
-                                     d_jdetail.data_ptr(), m, sync=False)
-            ctx.adam7_many_device(d_scr.data_ptr(), q[7], file_ptr, q[8], q[9], q[10], q[11], q[12], d_astatus.data_ptr(), 0, len(jj), sync=False)
-        if expand is not None:
-            ctx.expand_many_device(d_file.data_ptr(), pix_ptr, d_pal.data_ptr(), d_desc.data_ptr(), d_xstatus.data_ptr(), d_xdetail.data_ptr(), n,
-                                   sync=False)
-        ctx.sync()
-        bad_index = {}  # place in good -> (row, x, the index found there) of an image the expansion refused
-        if expand is not None:
-            xstatus, xdetail = d_xstatus.cpu().numpy().view(np.int32), d_xdetail.cpu().numpy().view(np.uint32).reshape(n, 2)
-            for j in np.flatnonzero(xstatus != _ffi.OK):
-                row, x, depth = int(xdetail[j, 0]), int(xdetail[j, 1]), good[j][1].bit_depth
-                if int(xstatus[j]) != _ffi.E_PALETTE:
-                    bad_index[int(j)] = None
-                    continue
-                byte = int(d_file[int(file_off[j]) + row * int(file_stride[j]) + x * depth // 8])  # (one byte back: the index itself)
-                bad_index[int(j)] = (row, x, (byte >> (8 - depth - x * depth % 8)) & ((1 << depth) - 1))
-        pass_error = {}  # place in good -> what its passes and its deinterlacing say, the first pass in pass order first
-        if laced:
-            jstatus, jdetail = d_jstatus.cpu().numpy().view(np.int32), d_jdetail.cpu().numpy().view(np.uint32).reshape(m, 2)
-            astatus = d_astatus.cpu().numpy().view(np.int32)
-            at = 0
-            for i, (j, passes) in enumerate(laced):
-                for t, (pno, _ph, _prb) in enumerate(passes):
-                    if j not in pass_error and int(jstatus[at + t]) != _ffi.OK:
-                        pass_error[j] = (pno, int(jstatus[at + t]), int(jdetail[at + t, 0]), int(jdetail[at + t, 1]))
-                if j not in pass_error and int(astatus[i]) != _ffi.OK:
-                    pass_error[j] = (0, int(astatus[i]), 0, 0)
-                at += len(passes)
-        out_len = d_out_len.cpu().numpy().view(np.uint64)
-        status = d_status.cpu().numpy().view(np.int32).reshape(2, n)
-        detail = d_detail.cpu().numpy().view(np.uint32).reshape(2, n, 2)
-        pixels = d_pix.cpu().numpy() if d_pix is not None else None  # the one copy out
-    finally:
-        ain.close()
+    lay = _layout(good, laced, expand, device_out)
+    out_len, blocks, pixels, bad_index = _run(ctx or default_context(), good, laced, lay, expand, int(device_out[0]) if device_out is not None else None)
+    pass_error, (dstatus, ddetail) = _pass_errors(laced, blocks), blocks["decode"]
+    ustatus, udetail = blocks.get("unfilter", (np.zeros(len(good), np.int32), np.zeros((len(good), 2), np.uint32)))
     for j, (k, img, z) in enumerate(good):
-        name, st, ust = names[k], int(status[0, j]), int(status[1, j])
-        if st == _ffi.E_OUT_TOO_SMALL:
-            results[k] = _format_error("%s: too much image data" % name)
-        elif st != _ffi.OK:
-            e = error_from_status(z, st, detail[0, j])
-            results[k] = DecompressionError(e.constructor, "%s: %s" % (name, e.message), e.status, e.detail)
-        elif int(out_len[j]) != int(dec_cap[j]):
-            results[k] = _format_error("%s: not enough image data" % name)
-        elif j in pass_error:
-            pno, pst, d0, d1 = pass_error[j]
-            if pno and pst == _ffi.E_FILTER:
-                results[k] = DecompressionError("FormatError", "%s: pass %d: row %d has filter type %d" % (name, pno, d0, d1), pst, (d0, d1))
-            else:
-                results[k] = _format_error("%s: the image's passes could not be put together" % name)
-        elif ust == _ffi.E_FILTER:
-            results[k] = DecompressionError("FormatError", "%s: row %d has filter type %d" % (name, int(detail[1, j, 0]), int(detail[1, j, 1])),
-                                            ust, (int(detail[1, j, 0]), int(detail[1, j, 1])))
-        elif ust != _ffi.OK:
-            results[k] = _format_error("%s: not enough image data" % name)
-        elif j in bad_index:
-            if bad_index[j] is None:
-                results[k] = _format_error("%s: the image's pixels could not be expanded" % name)
-            else:
-                row, x, index = bad_index[j]
-                results[k] = DecompressionError("FormatError", "%s: row %d, pixel %d: palette index %d of %d" % (name, row, x, index, len(img.palette) // 3),
-                                                _ffi.E_PALETTE, (row, x))
-        else:
+        results[k] = _verdict(names[k], img, z, (int(dstatus[j]), ddetail[j]), (int(ustatus[j]), udetail[j]), pass_error.get(j), bad_index.get(j),
+                              int(out_len[j]), int(lay.dec_cap[j]))
+        if results[k] is None:
             if pixels is not None:
-                o = int(pix_off[j])
-                flat = pixels[o:o + int(pix[j])].copy()
+                flat = pixels[int(lay.pix_off[j]):int(lay.pix_off[j]) + int(lay.pix[j])].copy()
                 img.data = _shape(img, flat) if expand is None else flat.reshape(img.height, img.width, _EXPAND[expand][1])
             img.expanded = expand
             results[k] = img
@@ -415,7 +429,7 @@ def read_png_batch(blobs_or_paths, expand: str = "rgb8", adam7: bool = False, ct
     blobs, sizes, errors = [], [], {}
     for k, src in enumerate(blobs_or_paths):
         try:
-            blobs.append(_load(src)[1])
+            blobs.append(load(src)[1])
         except OSError as e:
             blobs.append(b"")
             errors[k] = e

@@ -31,7 +31,8 @@ from typing import List, Optional, Sequence, Tuple, Union
 import numpy as np
 
 from . import _ffi
-from .zlib import UNPREDICT_DESC, Context, DecompressionError, PinnedArena, default_context, error_from_status
+from ._batch import DeviceChain, load
+from .zlib import UNPREDICT_DESC, Context, DecompressionError, default_context, error_from_status
 
 _TYPE_SIZE = {1: 1, 2: 1, 3: 2, 4: 4, 5: 8, 6: 1, 7: 1, 8: 2, 9: 4, 10: 8, 11: 4, 12: 8, 13: 4, 16: 8, 17: 8, 18: 8}
 _UINT_FMT = {1: "B", 3: "H", 4: "I", 13: "I", 16: "Q", 18: "Q"}
@@ -312,72 +313,41 @@ def _page_jobs(f: int, blob: bytes, pg: TiffPage, base: int, stride: int, plane_
     return out
 
 
+def _job_error(j: _Job, st: int, detail, ust: int) -> Optional[DecompressionError]:
+    """What the decode (st, its detail pair) and the stage (ust) say of a job, or None."""
+    where = "page %d, %s %d: " % (j.page, "tile" if j.tiled else "strip", j.index)
+    if st == _ffi.OK and ust == _ffi.OK:
+        return None
+    if st == _ffi.E_OUT_TOO_SMALL:
+        return DecompressionError("FormatError", where + "too much image data", _ffi.E_FILTER)
+    if st != _ffi.OK:
+        e = error_from_status(j.blob[j.start:j.start + j.length], st, detail)
+        return DecompressionError(e.constructor, where + e.message, e.status, e.detail)
+    if ust == _ffi.E_TRUNCATED:
+        return DecompressionError("FormatError", where + "not enough image data", _ffi.E_FILTER)
+    return DecompressionError("FormatError", where + "the rows could not be reconstructed", _ffi.E_FILTER)
+
+
 def _run(ctx: Context, jobs: List[_Job], total_pix: int, out_ptr: Optional[int]):
-    """The two launches over the jobs.  Returns (the pixel buffer on the host or None, {job: its error text and DecompressionError
-    fields}).  out_ptr: the jobs' dst_off count from this device address and nothing is copied out."""
-    import torch
-    n = len(jobs)
-    pad = lambda a: (a + np.uint64(15)) & ~np.uint64(15)  # noqa: E731
-    in_len = np.array([j.length for j in jobs], dtype=np.uint64)
-    dec_cap = np.array([j.rows * j.srb for j in jobs], dtype=np.uint64)
-    in_off, dec_off = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64)
-    in_off[1:] = np.cumsum(pad(in_len))[:-1]
-    dec_off[1:] = np.cumsum(pad(dec_cap + np.uint64(4)))[:-1]  # (4: a stream that decodes to MORE than its capacity claims no neighbour's dword)
-    tot_in = int(in_off[-1] + pad(in_len)[-1]) + 16
-    tot_dec = int(dec_off[-1] + pad(dec_cap + np.uint64(4))[-1]) + 16
-    desc = np.zeros(n, dtype=UNPREDICT_DESC)
-    desc["src_off"] = dec_off
-    for k, j in enumerate(jobs):
-        d = desc[k]
+    """The two launches over the jobs.  Returns (the pixel buffer on the host or None, {job: its DecompressionError}).  out_ptr:
+    the jobs' dst_off count from this device address and nothing is copied out."""
+    n, desc = len(jobs), np.zeros(len(jobs), dtype=UNPREDICT_DESC)
+    for d, j in zip(desc, jobs):
         d["dst_off"], d["dst_stride"], d["src_row_bytes"], d["rows"] = j.dst_off, j.dst_stride, j.srb, j.rows
         d["win_row"], d["win_rows"], d["win_byte"], d["win_bytes"] = j.window
         d["predictor"], d["sample_bytes"], d["samples"], d["big_endian"] = j.predictor, j.sample_bytes, j.samples, int(j.big_endian)
-    dev = torch.device("cuda", ctx.device)
-    ain = PinnedArena(tot_in)
-    try:
-        for k, j in enumerate(jobs):
-            ain.a[int(in_off[k]):int(in_off[k]) + j.length] = np.frombuffer(j.blob, dtype=np.uint8, count=j.length, offset=j.start)
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8)).to(dev)  # noqa: E731
-        d_in = up(ain.a[:tot_in])
-        d_meta = [up(a) for a in (in_off, in_len, dec_off, dec_cap, desc)]
-        d_dec = torch.empty(tot_dec, dtype=torch.uint8, device=dev)
-        d_pix = torch.empty(total_pix + 16, dtype=torch.uint8, device=dev) if out_ptr is None else None
-        d_out_len = torch.zeros(8 * n, dtype=torch.uint8, device=dev)
-        d_status = torch.zeros(2 * 4 * n, dtype=torch.uint8, device=dev)  # the decode's, the stage's
-        d_detail = torch.zeros(2 * 8 * n, dtype=torch.uint8, device=dev)
-        torch.cuda.synchronize(dev)
-        p = [t.data_ptr() for t in d_meta]
-        ctx.decompress_many_device(d_in.data_ptr(), p[0], p[1], d_dec.data_ptr(), p[2], p[3], d_out_len.data_ptr(), d_status.data_ptr(),
-                                   d_detail.data_ptr(), 0, 0, n, sync=False)
-        ctx.unpredict_many_device(d_dec.data_ptr(), d_out_len.data_ptr(), out_ptr if out_ptr is not None else d_pix.data_ptr(), p[4],
-                                  d_status.data_ptr() + 4 * n, d_detail.data_ptr() + 8 * n, n, sync=False)
-        ctx.sync()
-        status = d_status.cpu().numpy().view(np.int32).reshape(2, n)
-        detail = d_detail.cpu().numpy().view(np.uint32).reshape(2, n, 2)
-        pixels = d_pix.cpu().numpy() if d_pix is not None else None  # the one copy out
-    finally:
-        ain.close()
-    errors = {}
-    for k in np.flatnonzero((status[0] != _ffi.OK) | (status[1] != _ffi.OK)):
-        j, st, ust = jobs[k], int(status[0, k]), int(status[1, k])
-        where = "page %d, %s %d: " % (j.page, "tile" if j.tiled else "strip", j.index)
-        if st == _ffi.E_OUT_TOO_SMALL:
-            errors[int(k)] = DecompressionError("FormatError", where + "too much image data", _ffi.E_FILTER)
-        elif st != _ffi.OK:
-            e = error_from_status(j.blob[j.start:j.start + j.length], st, detail[0, k])
-            errors[int(k)] = DecompressionError(e.constructor, where + e.message, e.status, e.detail)
-        elif ust == _ffi.E_TRUNCATED:
-            errors[int(k)] = DecompressionError("FormatError", where + "not enough image data", _ffi.E_FILTER)
-        else:
-            errors[int(k)] = DecompressionError("FormatError", where + "the rows could not be reconstructed", _ffi.E_FILTER)
-    return pixels, errors
-
-
-def _load(src) -> Tuple[Optional[str], bytes]:
-    if isinstance(src, (bytes, bytearray, memoryview)):
-        return None, bytes(src)
-    with open(src, "rb") as f:
-        return os.fspath(src), f.read()
+    with DeviceChain(ctx, [(j.blob, j.start, j.length) for j in jobs], [j.rows * j.srb for j in jobs]) as ch:
+        pix = ch.scratch(total_pix + 16) if out_ptr is None else None
+        desc["src_off"] = ch.dec_off  # (job k reads its strip or tile where the decode put it)
+        desc_ptr = ch.upload(desc)
+        stage_status, stage_detail = ch.results("unpredict", n)
+        ch.decode()
+        ctx.unpredict_many_device(ch.dec_ptr, ch.out_len_ptr, out_ptr if pix is None else pix.data_ptr(), desc_ptr, stage_status, stage_detail, n, sync=False)
+        blocks = ch.finish()
+        pixels = pix.cpu().numpy() if pix is not None else None  # the one copy out
+    (status, detail), (ustatus, _udetail) = blocks["decode"], blocks["unpredict"]
+    bad = np.flatnonzero((status != _ffi.OK) | (ustatus != _ffi.OK))
+    return pixels, {int(k): _job_error(jobs[k], int(status[k]), detail[k], int(ustatus[k])) for k in bad}
 
 
 def _named(name: str, e: DecompressionError) -> DecompressionError:
@@ -396,7 +366,7 @@ def read_tiff_many(blobs_or_paths: Sequence[Union[str, os.PathLike, bytes, bytea
     for f, src in enumerate(blobs_or_paths):
         name = "#%d" % f
         try:
-            path, blob = _load(src)
+            path, blob = load(src)
             name = path or name
             pages = parse_tiff(blob, name)
             for pg in pages:
@@ -446,7 +416,7 @@ def read_tiff(blob_or_path, page: int = 0, ctx: Optional[Context] = None) -> Tif
 def read_tiff_region(blob_or_path, page: int, y0: int, x0: int, h: int, w: int, ctx: Optional[Context] = None) -> np.ndarray:
     """The rectangle of h rows from y0 and w pixels from x0 of a page: read_tiff(...).data[y0:y0 + h, x0:x0 + w] ([:, y0:.., x0:..] of a
     PlanarConfiguration 2 page), decoding only the strips or tiles that cover it; each is clipped to the rectangle on the device."""
-    path, blob = _load(blob_or_path)
+    path, blob = load(blob_or_path)
     name = path or "#0"
     pages = parse_tiff(blob, name)
     if not 0 <= page < len(pages):

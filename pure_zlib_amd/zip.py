@@ -23,6 +23,7 @@ import numpy as np
 
 from . import _ffi
 from . import split as _split
+from ._batch import pack
 from .zlib import Context, DecompressionError, PinnedArena, default_context, error_from_status
 
 _LOCAL_SIG = b"PK\x03\x04"
@@ -91,13 +92,7 @@ def _scan(src, ctx: Optional[Context], strict: bool, split: Optional[int] = None
         n = len(deflated)
         in_len = np.array([zi.compress_size for zi, _ in deflated], dtype=np.uint64)
         out_cap = np.array([zi.file_size for zi, _ in deflated], dtype=np.uint64)
-        pad = lambda a: (a + np.uint64(15)) & ~np.uint64(15)  # noqa: E731  (16-byte aligned extents: the wide store path)
-        in_off = np.zeros(n, dtype=np.uint64)
-        out_off = np.zeros(n, dtype=np.uint64)
-        in_off[1:] = np.cumsum(pad(in_len))[:-1]
-        out_off[1:] = np.cumsum(pad(out_cap))[:-1]
-        tot_in = int(in_off[-1] + pad(in_len)[-1]) + 16
-        tot_out = int(out_off[-1] + pad(out_cap)[-1]) + 16
+        (in_off, tot_in), (out_off, tot_out) = pack(in_len), pack(out_cap)
         ain, aout = PinnedArena(tot_in), PinnedArena(tot_out)
         try:
             for k, (zi, at) in enumerate(deflated):

@@ -17,6 +17,7 @@ from typing import List, Optional, Sequence, Union
 import numpy as np
 
 from . import _ffi
+from ._batch import pack
 
 # ---- DecompressionError (Monad.hs:87-104) -------------------------------------------------------
 
@@ -501,10 +502,6 @@ def _to_chunks(x: LazyByteString) -> List[bytes]:
     return [bytes(c) for c in x if len(c)]  # a lazy ByteString never holds empty chunks
 
 
-def _align(x, a=256):
-    return (x + a - 1) // a * a
-
-
 def decompress_many(streams: Sequence[LazyByteString], ctx: Optional[Context] = None,
                     size_hint: Optional[Sequence[int]] = None, gzip: bool = False,
                     zdict: Optional[Sequence[Optional[bytes]]] = None) -> List[Either]:
@@ -535,24 +532,18 @@ def _decompress_many(streams, ctx, size_hint, gzip, zdict, raw=False, crc32=Fals
         if not todo:
             break
         m = len(todo)
-        in_off = np.zeros(m, dtype=np.uint64)
         in_len = np.array([len(flat[i]) for i in todo], dtype=np.uint64)
-        out_off = np.zeros(m, dtype=np.uint64)
         out_cap = np.array([caps[i] for i in todo], dtype=np.uint64)
-        ipos = opos = 0
-        for k in range(m):  # 16-byte aligned extents: the wide store path
-            in_off[k], out_off[k] = ipos, opos
-            ipos += _align(int(in_len[k]), 16)
-            opos += _align(int(out_cap[k]), 16)
+        (in_off, tot_in), (out_off, tot_out) = pack(in_len), pack(out_cap)
         # packed into page-locked arenas (PZG_HOST_PINNED: the library then stages nothing a second time); preset dictionaries
         # and a system that will not lock the memory take the staged path over ordinary arrays
         in_buf = out_buf = None
         if zdict is None:
-            in_buf, out_buf = _arena("in", ipos + 16), _arena("out", opos + 16)
+            in_buf, out_buf = _arena("in", tot_in), _arena("out", tot_out)
         pinned = in_buf is not None and out_buf is not None
         if not pinned:
-            in_buf = np.zeros(ipos + 16, dtype=np.uint8)
-            out_buf = np.zeros(opos + 16, dtype=np.uint8)
+            in_buf = np.zeros(tot_in, dtype=np.uint8)
+            out_buf = np.zeros(tot_out, dtype=np.uint8)
         for k, i in enumerate(todo):
             in_buf[int(in_off[k]):int(in_off[k]) + len(flat[i])] = np.frombuffer(flat[i], dtype=np.uint8)
         dict_args = {}
