@@ -681,6 +681,71 @@ PZG_API int pzg_unpredict_many(pzg_ctx *ctx,
         uint32_t n, uint32_t flags);         /* 0, PZG_DEVICE_PTRS, PZG_DEVICE_PTRS | PZG_ASYNC */
 
 /*
+ * pzg_unshuffle_many (0.5): EXTENSION -- the byte-plane transpose ("shuffle") undone, with or without a byte-wise running sum in front
+ * of it, and strips or tiles clipped to a window: all n jobs in one launch, the rows of a job spread over several wavefronts.  With
+ * the sum it is TIFF's floating-point predictor (Predictor 3, TIFF Technical Note 3; libtiff fpAcc); the transpose alone is the
+ * shuffle filter that HDF5, Zarr (numcodecs Shuffle) and Blosc put in front of zlib.  One job is one strip, tile or chunk as it was
+ * decoded; nothing in the call knows of TIFF's tags.
+ *   desc[i]     one job (pzg_unshuffle_desc below; its reserved bytes and words are 0).  Source, window and delivery are those of
+ *               pzg_unpredict_desc, field for field in the first 48 bytes:
+ *     source      `rows` stored rows of src_row_bytes = n x elem_bytes bytes, dense, at src_base + src_off, at any alignment.
+ *     window      the rows [win_row, win_row + win_rows) of the job and, of each, the bytes [win_byte, win_byte + win_bytes) of the
+ *                 RECONSTRUCTED row: it may start or end inside an element.
+ *     delivery    window row r at dst_base + dst_off + r * dst_stride (dst_stride >= win_bytes).  The bytes between win_bytes and
+ *                 the stride and everything outside the extents are untouched.  The dst extents overlap neither each other nor src.
+ *     elem_bytes  B: 2, 4 or 8.  A stored row is B planes of n bytes.
+ *     sum_stride  S.  1 .. 4: first t[k] = stored[k] + t[k - S] modulo 256 for k >= S over ALL n x B bytes of the row -- the sum runs
+ *                 straight across the planes' boundaries; n is a multiple of S (the stored samples of a pixel, 1 for a separate
+ *                 plane).  0: no sum, t = stored: the transpose alone.
+ *     reverse     byte j of output element i is t[j * n + i] where reverse is 0 (plane j is byte j: a big-endian TIFF; HDF5 / Zarr
+ *                 shuffle) and t[(B - 1 - j) * n + i] where it is 1 (a little-endian TIFF: plane 0 holds the most significant bytes).
+ *   src_len[i]  the bytes of job i that src holds: a separate array so that it can be the out_len array a preceding
+ *               pzg_decompress_many(... PZG_ASYNC) wrote.
+ *   status[i]   PZG_OK
+ *               PZG_E_TRUNCATED  src_len[i] < rows * src_row_bytes: d0 is the number of stored rows that lie wholly inside
+ *                                src_len[i]; those of them that fall in the window are delivered.
+ *               rows, src_row_bytes, win_rows or win_bytes of 0: PZG_OK, nothing read or written.
+ *   detail      2n words (d0, d1 per job), or NULL: 0, 0 of a PZG_OK job.
+ * flags: as for pzg_unpredict_many, in both forms; pzg_decompress_many, pzg_unpredict_many, pzg_unshuffle_many and pzg_sync chain
+ * without a host round trip.  pzg_last_kernel_ms reports the launch.
+ * PZG_RC_BAD_ARG: n == 0, any other flag, a null array, a context of several devices; with host pointers also, of a job that is not
+ * empty, an elem_bytes outside the list, a sum_stride above 4, a reverse above 1, a src_row_bytes that is no multiple of elem_bytes,
+ * an n that is no multiple of sum_stride, a window that reaches outside the stored job and a dst_stride below win_bytes.  Device
+ * arrays are not read by the host: there such a job gets PZG_E_FILTER with d0 = 0xffffffff and
+ * d1 = elem_bytes << 16 | sum_stride << 8 | reverse, and nothing of it is read or written.
+ * Offsets and strides are 64-bit.  Nothing is read but the aligned dwords that hold bytes of
+ * src_off .. + min(src_len[i], rows * src_row_bytes): with a sum every byte of the rows delivered, without one only the elements
+ * that hold the window's bytes, from each plane.
+ */
+typedef struct pzg_unshuffle_desc {
+    uint64_t src_off;                  /*  0 */
+    uint64_t dst_off, dst_stride;      /*  8, 16 */
+    uint32_t src_row_bytes, rows;      /* 24, 28 */
+    uint32_t win_row, win_rows;        /* 32, 36 */
+    uint32_t win_byte, win_bytes;      /* 40, 44 */
+    uint8_t elem_bytes, sum_stride;    /* 48, 49 */
+    uint8_t reverse, reserved0;        /* 50, 51: 0 */
+    uint32_t reserved[3];              /* 52: 0 */
+} pzg_unshuffle_desc;
+#if defined(__cplusplus)
+static_assert(sizeof(pzg_unshuffle_desc) == 64 && offsetof(pzg_unshuffle_desc, dst_off) == 8 && offsetof(pzg_unshuffle_desc, dst_stride) == 16 &&
+              offsetof(pzg_unshuffle_desc, src_row_bytes) == 24 && offsetof(pzg_unshuffle_desc, rows) == 28 && offsetof(pzg_unshuffle_desc, win_row) == 32 &&
+              offsetof(pzg_unshuffle_desc, win_rows) == 36 && offsetof(pzg_unshuffle_desc, win_byte) == 40 && offsetof(pzg_unshuffle_desc, win_bytes) == 44 &&
+              offsetof(pzg_unshuffle_desc, elem_bytes) == 48 && offsetof(pzg_unshuffle_desc, sum_stride) == 49 && offsetof(pzg_unshuffle_desc, reverse) == 50 &&
+              offsetof(pzg_unshuffle_desc, reserved0) == 51 && offsetof(pzg_unshuffle_desc, reserved) == 52, "pzg_unshuffle_desc is 64 bytes, laid out as commented");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(pzg_unshuffle_desc) == 64 && offsetof(pzg_unshuffle_desc, src_row_bytes) == 24 && offsetof(pzg_unshuffle_desc, elem_bytes) == 48,
+               "pzg_unshuffle_desc is 64 bytes, laid out as commented");
+#endif
+
+PZG_API int pzg_unshuffle_many(pzg_ctx *ctx,
+        const uint8_t *src_base, const uint64_t *src_len,   /* n */
+        uint8_t *dst_base,
+        const pzg_unshuffle_desc *desc,      /* n */
+        int32_t *status, uint32_t *detail,   /* detail: 2n, or NULL */
+        uint32_t n, uint32_t flags);         /* 0, PZG_DEVICE_PTRS, PZG_DEVICE_PTRS | PZG_ASYNC */
+
+/*
  * decompressIncremental / ZlibDecoder (Zlib.hs:3-8, Monad.hs:163-197; driver Deflate.hs:30-48), batched: a pzg_decoder
  * is n suspended zlib decoders (gzip or raw ones: pzg_decoder_create_format) living on the device (a one-device context).  pzg_decoder_feed continues the decoders
  * idx[0..m) (idx = NULL: all n, m ignored) -- one launch, one wavefront per decoder -- as far as their input and

@@ -59,7 +59,7 @@ SYMBOLS = [
     "pzg_decoder_create", "pzg_decoder_create_format", "pzg_decoder_destroy", "pzg_decoder_reset", "pzg_decoder_feed", "pzg_decoder_last_feed_ms", "pzg_shutdown", "pzg_set_stream", "pzg_reset_stream", "pzg_set_option", "pzg_sync", "pzg_decompress_many", "pzg_decompress",
     "pzg_adler32", "pzg_error_message", "pzg_last_kernel_ms", "pzg_strerror", "pzg_last_error", "pzg_version",
     "pzg_index_build", "pzg_decompress_many_segments", "pzg_index_scan", "pzg_index_scan_many", "pzg_gzip_find_members", "pzg_gzip_layout",
-    "pzg_unfilter_many", "pzg_adam7_many", "pzg_expand_many", "pzg_unpredict_many",
+    "pzg_unfilter_many", "pzg_adam7_many", "pzg_expand_many", "pzg_unpredict_many", "pzg_unshuffle_many",
 ]
 
 
@@ -84,6 +84,13 @@ class UnpredictDesc(C.Structure):
     _fields_ = [("src_off", C.c_uint64), ("dst_off", C.c_uint64), ("dst_stride", C.c_uint64), ("src_row_bytes", C.c_uint32), ("rows", C.c_uint32),
                 ("win_row", C.c_uint32), ("win_rows", C.c_uint32), ("win_byte", C.c_uint32), ("win_bytes", C.c_uint32), ("predictor", C.c_uint8),
                 ("sample_bytes", C.c_uint8), ("samples", C.c_uint8), ("big_endian", C.c_uint8), ("reserved", C.c_uint32 * 3)]
+
+
+class UnshuffleDesc(C.Structure):
+    """pzg_unshuffle_desc (include/pzg.h): one strip, tile or chunk of a pzg_unshuffle_many call, 64 bytes."""
+    _fields_ = [("src_off", C.c_uint64), ("dst_off", C.c_uint64), ("dst_stride", C.c_uint64), ("src_row_bytes", C.c_uint32), ("rows", C.c_uint32),
+                ("win_row", C.c_uint32), ("win_rows", C.c_uint32), ("win_byte", C.c_uint32), ("win_bytes", C.c_uint32), ("elem_bytes", C.c_uint8),
+                ("sum_stride", C.c_uint8), ("reverse", C.c_uint8), ("reserved0", C.c_uint8), ("reserved", C.c_uint32 * 3)]
 
 
 class PzgError(RuntimeError):
@@ -165,6 +172,9 @@ def lib():
     if hasattr(L, "pzg_unpredict_many"):
         L.pzg_unpredict_many.argtypes = [C.c_void_p, vp, u64p, vp, vp, i32p, u32p, C.c_uint32, C.c_uint32]
         L.pzg_unpredict_many.restype = C.c_int
+    if hasattr(L, "pzg_unshuffle_many"):
+        L.pzg_unshuffle_many.argtypes = [C.c_void_p, vp, u64p, vp, vp, i32p, u32p, C.c_uint32, C.c_uint32]
+        L.pzg_unshuffle_many.restype = C.c_int
     L.pzg_decompress_many_sharded.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
     L.pzg_decompress_many_sharded.restype = C.c_int
     L.pzg_decoder_create.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]

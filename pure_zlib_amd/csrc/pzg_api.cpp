@@ -50,6 +50,7 @@
 #include "pzg_unfilter_kernel.h"  // (unfilter_kernel and its launcher; unfilter_core.h: its statuses, and what it takes for a legal bpp)
 #include "pzg_expand_kernel.h"    // (expand_kernel and its launcher; expand_core.h: its statuses, a legal geometry, the bytes of a row)
 #include "pzg_unpredict_kernel.h" // (unpredict_kernel and its launcher; unpredict_core.h: its statuses, a legal geometry, the rows inside src_len)
+#include "pzg_unshuffle_kernel.h" // (unshuffle_kernel and its launcher; unshuffle_core.h: the same of the byte-plane stage)
 #include "pzg_adam7_kernel.h"     // (adam7_kernel and its launcher; adam7_core.h: its statuses, a legal geometry, an image's source extent)
 
 namespace {
@@ -1156,7 +1157,7 @@ int stream_launch(pzg_ctx *ctx, Shard &sh, uint32_t flags, Before &&before, Laun
 }
 inline int nothing_before() { return PZG_RC_OK; }
 
-// ---- the image stages (pzg_unfilter_many, pzg_adam7_many, pzg_expand_many, pzg_unpredict_many).  What all of them take: one device, PZG_DEVICE_PTRS, PZG_ASYNC with it
+// ---- the image stages (pzg_unfilter_many, pzg_adam7_many, pzg_expand_many, pzg_unpredict_many, pzg_unshuffle_many).  What all of them take: one device, PZG_DEVICE_PTRS, PZG_ASYNC with it
 inline bool stage_call_ok(const pzg_ctx *ctx, uint32_t n, uint32_t flags)
 {
     return ctx_live(ctx) && n != 0 && !(flags & ~(PZG_DEVICE_PTRS | PZG_ASYNC)) && (!(flags & PZG_ASYNC) || (flags & PZG_DEVICE_PTRS)) && ctx->shards.size() == 1;
@@ -2089,6 +2090,57 @@ int pzg_unpredict_many(pzg_ctx *ctx, const uint8_t *src_base, const uint64_t *sr
             a.src_len = m_slen.in(dm);
         },
         pzg::launch_unpredict,
+        // the window's rows in front of the first stored row that does not lie wholly inside src_len
+        [&](int32_t st, uint32_t d0, uint32_t rows, uint32_t i) { return st == PZG_OK ? rows : st == PZG_E_TRUNCATED && d0 > hd[i].win_row ? d0 - hd[i].win_row : 0u; });
+}
+
+// The byte-plane transpose and TIFF Predictor 3 (unshuffle_core.h): pzg_unpredict_many's two forms with another kernel.
+int pzg_unshuffle_many(pzg_ctx *ctx, const uint8_t *src_base, const uint64_t *src_len, uint8_t *dst_base, const pzg_unshuffle_desc *desc, int32_t *status,
+                       uint32_t *detail, uint32_t n, uint32_t flags)
+{
+    using U = pzg::Unshuffle;
+    static_assert(U::ST_FILTER == PZG_E_FILTER && U::ST_TRUNCATED == PZG_E_TRUNCATED && U::ST_OK == PZG_OK, "the core's statuses are the header's");
+    static_assert(sizeof(U::Desc) == sizeof(pzg_unshuffle_desc) && offsetof(U::Desc, dst_off) == offsetof(pzg_unshuffle_desc, dst_off) &&
+                      offsetof(U::Desc, dst_stride) == offsetof(pzg_unshuffle_desc, dst_stride) &&
+                      offsetof(U::Desc, src_row_bytes) == offsetof(pzg_unshuffle_desc, src_row_bytes) && offsetof(U::Desc, rows) == offsetof(pzg_unshuffle_desc, rows) &&
+                      offsetof(U::Desc, win_row) == offsetof(pzg_unshuffle_desc, win_row) && offsetof(U::Desc, win_rows) == offsetof(pzg_unshuffle_desc, win_rows) &&
+                      offsetof(U::Desc, win_byte) == offsetof(pzg_unshuffle_desc, win_byte) && offsetof(U::Desc, win_bytes) == offsetof(pzg_unshuffle_desc, win_bytes) &&
+                      offsetof(U::Desc, elem_bytes) == offsetof(pzg_unshuffle_desc, elem_bytes) &&
+                      offsetof(U::Desc, sum_stride) == offsetof(pzg_unshuffle_desc, sum_stride) && offsetof(U::Desc, reverse) == offsetof(pzg_unshuffle_desc, reverse) &&
+                      offsetof(U::Desc, reserved0) == offsetof(pzg_unshuffle_desc, reserved0) && offsetof(U::Desc, reserved) == offsetof(pzg_unshuffle_desc, reserved),
+                  "the core's descriptor is the header's");
+    if (!stage_call_ok(ctx, n, flags) || !src_base || !src_len || !dst_base || !desc || !status) return PZG_RC_BAD_ARG;
+    if (flags & PZG_DEVICE_PTRS)
+        return guarded(ctx, "pzg_unshuffle_many", [&]() -> int {
+            const pzg::UnshuffleArgs a{src_base, src_len, dst_base, desc, status, detail, n};
+            return stream_launch(ctx, *ctx->shards[0], flags, nothing_before, [&](hipStream_t s) { return pzg::launch_unshuffle(a, s); });
+        });
+    // host pointers: what the device form leaves to the kernel
+    const U::Desc *hd = (const U::Desc *)(const void *)desc;
+    for (uint32_t i = 0; i < n; ++i)
+        if (!U::empty(hd[i]) && !U::geometry_ok(hd[i])) return PZG_RC_BAD_ARG;
+    pzg::MetaCursor c;
+    const auto m_desc = c.take<U::Desc>(n);
+    const auto m_slen = c.take<uint64_t>(n);
+    const auto extent = [&](uint32_t i) {
+        const U::Desc &D = hd[i];
+        if (U::empty(D)) return pzg::StageExtent{};
+        return pzg::StageExtent{D.src_off, std::min(src_len[i], (uint64_t)D.rows * D.src_row_bytes), D.dst_off, D.dst_stride, D.win_bytes, D.win_rows, false};
+    };
+    return image_stage_host(
+        ctx, "pzg_unshuffle_many", n, src_base, dst_base, status, detail, c, extent,
+        [&](uint8_t *hm, uint8_t *dm, const pzg::StageSpans &sp, pzg::UnshuffleArgs &a) {
+            U::Desc *sd = m_desc.in(hm);
+            for (uint32_t i = 0; i < n; ++i) {
+                sd[i] = hd[i];
+                sd[i].src_off = sp.src_at(extent(i));
+                sd[i].dst_off = sp.dst_at(extent(i));
+            }
+            memcpy(m_slen.in(hm), src_len, 8 * (size_t)n);
+            a.desc = m_desc.in(dm);
+            a.src_len = m_slen.in(dm);
+        },
+        pzg::launch_unshuffle,
         // the window's rows in front of the first stored row that does not lie wholly inside src_len
         [&](int32_t st, uint32_t d0, uint32_t rows, uint32_t i) { return st == PZG_OK ? rows : st == PZG_E_TRUNCATED && d0 > hd[i].win_row ? d0 - hd[i].win_row : 0u; });
 }

@@ -235,6 +235,19 @@ struct UnpredictArgs {
     uint32_t n;
 };
 
+// The byte-plane transpose and TIFF Predictor 3 (pzg_unshuffle_kernel.h, unshuffle_core.h; compiled with pzg_api.cpp): the rows of a job
+// over the grid's y.  Every pointer is device memory.  desc: n descriptors of 64 bytes, pzg_unshuffle_desc as the core sees it
+// (Unshuffle::Desc).
+struct UnshuffleArgs {
+    const uint8_t *src_base;
+    const uint64_t *src_len;  // n
+    uint8_t *dst_base;
+    const void *desc;         // n
+    int32_t *status;          // n
+    uint32_t *detail;         // 2n or null
+    uint32_t n;
+};
+
 // partials: 3 * 4 * ceil(max_waves / 4) uint32 of device scratch
 hipError_t launch_adler32(const uint8_t *buf, uint64_t len, uint32_t init, uint32_t *partials, uint32_t max_waves,
                           uint32_t *out, hipStream_t stream);

@@ -7,20 +7,28 @@ launch behind it on the same stream, which takes the decode's out_len array as i
 TIFF 6.0 section 14) is undone on the device and every tile is clipped to the image as it is delivered into the page's rows.  One
 sync, and one copy out of the pixels alone.  The host parses the IFDs; nothing is inflated on the CPU.  Device memory is held in
 torch tensors.
+With float_predictor=True the floating-point predictor (Predictor 3, TIFF Technical Note 3: what GDAL and libtiff write for elevation
+models and other float rasters) is read as well: the strips and tiles of such pages go through ONE pzg_unshuffle_many launch -- a
+byte-wise running sum along the row, then the byte planes transposed back into elements -- behind the pzg_unpredict_many launch of
+the others, on the same stream and with the same out_len array; a batch without such pages issues the launches it always did.
 
     parse_tiff(blob)                  -> [TiffPage]               (pure Python, no GPU; ValueError names the page and the tag)
     read_tiff_many(blobs_or_paths)    -> [[TiffImage per page], or the DecompressionError / ValueError / NotImplementedError of that file]
     read_tiff(blob_or_path, page=0)   -> TiffImage                (raises)
     read_tiff_region(blob_or_path, page, y0, x0, h, w) -> np.ndarray   (only the strips or tiles that cover the rectangle are decoded)
     test_tiff_many(blobs_or_paths)    -> [(index_or_name, problem)]   (empty: every file is sound)
-    python -m pure_zlib_amd.tiff -t A.tif B.tif ...
+    python -m pure_zlib_amd.tiff -t [--float-predictor] A.tif B.tif ...
+    (each of the four readers takes float_predictor=False)
 
 Byte orders II and MM, classic TIFF and BigTIFF, strips and tiles, PlanarConfiguration 1 and 2, Predictor 1 and 2, 8/16/32/64-bit
-samples of any SampleFormat, and 1/2/4-bit single-sample images as packed rows.  `data` is the samples as the file stores them, in the
-file's byte order: PhotometricInterpretation, ExtraSamples, Orientation and ColorMap are reported, not interpreted.  Not done
-(NotImplementedError, for that file alone): any other compression, Predictor 3 (the floating-point predictor), FillOrder 2, unequal
-BitsPerSample, bits below 8 with several samples or with Predictor 2, Predictor 2 with bits outside 8/16/32/64 or with more than four
-chunky samples, subsampled YCbCr, a strip or tile of 4 GiB or more.
+samples of any SampleFormat, and 1/2/4-bit single-sample images as packed rows; with float_predictor=True Predictor 3 on
+16/32/64-bit floating-point samples, chunky with up to four samples or as separate planes.  `data` is the samples as the file stores
+them, in the file's byte order: PhotometricInterpretation, ExtraSamples, Orientation and ColorMap are reported, not interpreted.  Not
+done (NotImplementedError, for that file alone): any other compression, Predictor 3 (the floating-point predictor) without
+float_predictor=True, FillOrder 2, unequal BitsPerSample, bits below 8 with several samples or with Predictor 2, Predictor 2 with bits
+outside 8/16/32/64, Predictor 2 or 3 with more than four chunky samples, 24-bit floats, subsampled YCbCr, a strip or tile of 4 GiB or
+more.  Predictor 3 on samples that are not floating-point, or on 8-bit ones, is a ValueError (tags 317 / 339): libtiff refuses such
+files too.
 """
 import os
 import struct
@@ -32,7 +40,7 @@ import numpy as np
 
 from . import _ffi
 from ._batch import DeviceChain, load
-from .zlib import UNPREDICT_DESC, Context, DecompressionError, default_context, error_from_status
+from .zlib import UNPREDICT_DESC, UNSHUFFLE_DESC, Context, DecompressionError, default_context, error_from_status
 
 _TYPE_SIZE = {1: 1, 2: 1, 3: 2, 4: 4, 5: 8, 6: 1, 7: 1, 8: 2, 9: 4, 10: 8, 11: 4, 12: 8, 13: 4, 16: 8, 17: 8, 18: 8}
 _UINT_FMT = {1: "B", 3: "H", 4: "I", 13: "I", 16: "Q", 18: "Q"}
@@ -216,19 +224,22 @@ def parse_tiff(blob, name: str = "tiff") -> List[TiffPage]:
     return pages
 
 
-def _check_supported(name: str, pg: TiffPage) -> None:
+def _check_supported(name: str, pg: TiffPage, float_predictor: bool = False) -> None:
     where = "%s: page %d" % (name, pg.index)
     if pg.compression not in (8, 32946):
         raise NotImplementedError("%s: Compression %d (only Deflate, 8 and 32946, is read)" % (where, pg.compression))
-    if pg.predictor == 3:
+    if pg.predictor == 3 and not float_predictor:
         raise NotImplementedError("%s: Predictor 3 (the floating-point predictor) is not read" % where)
-    if pg.predictor not in (1, 2):
+    if pg.predictor not in (1, 2, 3):
         raise ValueError("%s: tag 317 (Predictor): %d" % (where, pg.predictor))
     if pg.fill_order != 1:
         raise NotImplementedError("%s: FillOrder %d is not read" % (where, pg.fill_order))
     if len(set(pg.bits_per_sample)) != 1:
         raise NotImplementedError("%s: unequal BitsPerSample %s" % (where, pg.bits_per_sample[:8]))
     bits = pg.bits
+    if pg.predictor == 3 and (pg.sample_format != 3 or bits <= 8):
+        raise ValueError("%s: tag 317 (Predictor) 3 with tag 339 (SampleFormat) %d and %d-bit samples: the floating-point predictor takes "
+                         "floating-point samples of 16, 32 or 64 bits" % (where, pg.sample_format, bits))
     if bits < 8:
         if bits not in (1, 2, 4):
             raise NotImplementedError("%s: %d bits per sample" % (where, bits))
@@ -240,6 +251,8 @@ def _check_supported(name: str, pg: TiffPage) -> None:
         raise NotImplementedError("%s: %d bits per sample" % (where, bits))
     if pg.predictor == 2 and pg.stored_samples > 4:
         raise NotImplementedError("%s: Predictor 2 with %d chunky samples per pixel" % (where, pg.stored_samples))
+    if pg.predictor == 3 and pg.stored_samples > 4:
+        raise NotImplementedError("%s: Predictor 3 with %d chunky samples per pixel" % (where, pg.stored_samples))
     if pg.photometric == 6 and pg.subsampling not in (None, (1, 1)):
         raise NotImplementedError("%s: YCbCr with subsampling %s" % (where, pg.subsampling))
     if pg.tile_length * pg.row_bytes(pg.tile_width) >= 1 << 32:
@@ -271,7 +284,8 @@ def _image(pg: TiffPage, flat: Optional[np.ndarray]) -> TiffImage:
 
 @dataclass
 class _Job:
-    """One strip or tile: where its stream lies in its file, and its pzg_unpredict_desc but for the offsets the launch gives it."""
+    """One strip or tile: where its stream lies in its file, and its pzg_unpredict_desc -- with Predictor 3 its pzg_unshuffle_desc:
+    sample_bytes is elem_bytes, samples sum_stride, a little-endian file reverse -- but for the offsets the launch gives it."""
     file: int
     page: int
     index: int
@@ -297,7 +311,7 @@ def _page_jobs(f: int, blob: bytes, pg: TiffPage, base: int, stride: int, plane_
     srb = pg.row_bytes(pg.tile_width)
     image_rb = pg.row_bytes(pg.width)
     ry, rx, rh, rw = rect if rect is not None else (0, 0, pg.height, image_rb)
-    sb, s = (pg.bits // 8, pg.stored_samples) if pg.predictor == 2 else (1, 1)
+    sb, s = (pg.bits // 8, pg.stored_samples) if pg.predictor in (2, 3) else (1, 1)
     per_plane = pg.across * pg.down
     for plane in range(pg.planes):
         for ty in range(ry // pg.tile_length, -(-(ry + rh) // pg.tile_length)):
@@ -329,25 +343,41 @@ def _job_error(j: _Job, st: int, detail, ust: int) -> Optional[DecompressionErro
 
 
 def _run(ctx: Context, jobs: List[_Job], total_pix: int, out_ptr: Optional[int]):
-    """The two launches over the jobs.  Returns (the pixel buffer on the host or None, {job: its DecompressionError}).  out_ptr:
-    the jobs' dst_off count from this device address and nothing is copied out."""
-    n, desc = len(jobs), np.zeros(len(jobs), dtype=UNPREDICT_DESC)
-    for d, j in zip(desc, jobs):
+    """The decode and the stage launches over the jobs: the Predictor 1 / 2 jobs go to pzg_unpredict_many, the Predictor 3 jobs to
+    pzg_unshuffle_many behind it, each launch only where it has jobs.  The decode takes the jobs with each kind contiguous, so that
+    both stages find their src_len in its out_len array; errors come back under the jobs' own indices.  Returns (the pixel buffer on
+    the host or None, {job: its DecompressionError}).  out_ptr: the jobs' dst_off count from this device address and nothing is
+    copied out."""
+    order = sorted(range(len(jobs)), key=lambda k: jobs[k].predictor == 3)  # (stable: file order within a kind)
+    run = [jobs[k] for k in order]
+    n = len(run)
+    nu = sum(1 for j in run if j.predictor != 3)
+    desc, fdesc = np.zeros(nu, dtype=UNPREDICT_DESC), np.zeros(n - nu, dtype=UNSHUFFLE_DESC)
+    for d, j in zip(list(desc) + list(fdesc), run):
         d["dst_off"], d["dst_stride"], d["src_row_bytes"], d["rows"] = j.dst_off, j.dst_stride, j.srb, j.rows
         d["win_row"], d["win_rows"], d["win_byte"], d["win_bytes"] = j.window
-        d["predictor"], d["sample_bytes"], d["samples"], d["big_endian"] = j.predictor, j.sample_bytes, j.samples, int(j.big_endian)
-    with DeviceChain(ctx, [(j.blob, j.start, j.length) for j in jobs], [j.rows * j.srb for j in jobs]) as ch:
+        if j.predictor == 3:
+            d["elem_bytes"], d["sum_stride"], d["reverse"] = j.sample_bytes, j.samples, int(not j.big_endian)
+        else:
+            d["predictor"], d["sample_bytes"], d["samples"], d["big_endian"] = j.predictor, j.sample_bytes, j.samples, int(j.big_endian)
+    with DeviceChain(ctx, [(j.blob, j.start, j.length) for j in run], [j.rows * j.srb for j in run]) as ch:
         pix = ch.scratch(total_pix + 16) if out_ptr is None else None
-        desc["src_off"] = ch.dec_off  # (job k reads its strip or tile where the decode put it)
-        desc_ptr = ch.upload(desc)
-        stage_status, stage_detail = ch.results("unpredict", n)
+        dst = out_ptr if pix is None else pix.data_ptr()
+        desc["src_off"], fdesc["src_off"] = ch.dec_off[:nu], ch.dec_off[nu:]  # (job k reads its strip or tile where the decode put it)
+        stages = []  # (the wrapper, the descriptors' address, status, detail, the first job, the jobs)
+        if nu:
+            stages.append((ctx.unpredict_many_device, ch.upload(desc)) + ch.results("unpredict", nu) + (0, nu))
+        if n - nu:
+            stages.append((ctx.unshuffle_many_device, ch.upload(fdesc)) + ch.results("unshuffle", n - nu) + (nu, n - nu))
         ch.decode()
-        ctx.unpredict_many_device(ch.dec_ptr, ch.out_len_ptr, out_ptr if pix is None else pix.data_ptr(), desc_ptr, stage_status, stage_detail, n, sync=False)
+        for launch, desc_ptr, stage_status, stage_detail, first, count in stages:
+            launch(ch.dec_ptr, ch.out_len_ptr + 8 * first, dst, desc_ptr, stage_status, stage_detail, count, sync=False)
         blocks = ch.finish()
         pixels = pix.cpu().numpy() if pix is not None else None  # the one copy out
-    (status, detail), (ustatus, _udetail) = blocks["decode"], blocks["unpredict"]
+    status, detail = blocks["decode"]
+    ustatus = np.concatenate([blocks[name][0] for name in ("unpredict", "unshuffle") if name in blocks])
     bad = np.flatnonzero((status != _ffi.OK) | (ustatus != _ffi.OK))
-    return pixels, {int(k): _job_error(jobs[k], int(status[k]), detail[k], int(ustatus[k])) for k in bad}
+    return pixels, {order[int(k)]: _job_error(run[k], int(status[k]), detail[k], int(ustatus[k])) for k in bad}
 
 
 def _named(name: str, e: DecompressionError) -> DecompressionError:
@@ -355,9 +385,11 @@ def _named(name: str, e: DecompressionError) -> DecompressionError:
 
 
 def read_tiff_many(blobs_or_paths: Sequence[Union[str, os.PathLike, bytes, bytearray, memoryview]], ctx: Optional[Context] = None,
-                   device_out: Optional[Tuple[int, Sequence[int], Sequence[int]]] = None) -> List[Union[List[TiffImage], Exception]]:
+                   device_out: Optional[Tuple[int, Sequence[int], Sequence[int]]] = None, float_predictor: bool = False) -> List[Union[List[TiffImage], Exception]]:
     """Per file the list of its pages, or in its place the exception that read_tiff would raise for it: a bad file never disturbs its
-    neighbours.  device_out = (ptr, offsets, strides), one entry per page in order -- the pages of all the files that parse_tiff
+    neighbours.  float_predictor=True: pages with Predictor 3 are read (floating-point samples of 16, 32 or 64 bits) -- their strips and
+    tiles go through one pzg_unshuffle_many launch behind the pzg_unpredict_many launch of the others; without it such a page is the
+    NotImplementedError it has always been.  device_out = (ptr, offsets, strides), one entry per page in order -- the pages of all the files that parse_tiff
     reads and the reader supports, counted through the batch: row y of that page lands at ptr + offsets[k] + y * strides[k] (plane p
     of a PlanarConfiguration 2 page H * strides[k] further on for every p) in device memory of the caller's (a torch tensor's
     data_ptr()), nothing is copied out and `data` is None."""
@@ -370,7 +402,7 @@ def read_tiff_many(blobs_or_paths: Sequence[Union[str, os.PathLike, bytes, bytea
             name = path or name
             pages = parse_tiff(blob, name)
             for pg in pages:
-                _check_supported(name, pg)
+                _check_supported(name, pg, float_predictor)
             places, mine = [], []
             for pg in pages:
                 rb = pg.row_bytes(pg.width)
@@ -403,9 +435,9 @@ def read_tiff_many(blobs_or_paths: Sequence[Union[str, os.PathLike, bytes, bytea
     return results
 
 
-def read_tiff(blob_or_path, page: int = 0, ctx: Optional[Context] = None) -> TiffImage:
+def read_tiff(blob_or_path, page: int = 0, ctx: Optional[Context] = None, float_predictor: bool = False) -> TiffImage:
     """One page of one file.  Raises what read_tiff_many would put in the file's place."""
-    r = read_tiff_many([blob_or_path], ctx)[0]
+    r = read_tiff_many([blob_or_path], ctx, float_predictor=float_predictor)[0]
     if isinstance(r, Exception):
         raise r
     if not 0 <= page < len(r):
@@ -413,7 +445,7 @@ def read_tiff(blob_or_path, page: int = 0, ctx: Optional[Context] = None) -> Tif
     return r[page]
 
 
-def read_tiff_region(blob_or_path, page: int, y0: int, x0: int, h: int, w: int, ctx: Optional[Context] = None) -> np.ndarray:
+def read_tiff_region(blob_or_path, page: int, y0: int, x0: int, h: int, w: int, ctx: Optional[Context] = None, float_predictor: bool = False) -> np.ndarray:
     """The rectangle of h rows from y0 and w pixels from x0 of a page: read_tiff(...).data[y0:y0 + h, x0:x0 + w] ([:, y0:.., x0:..] of a
     PlanarConfiguration 2 page), decoding only the strips or tiles that cover it; each is clipped to the rectangle on the device."""
     path, blob = load(blob_or_path)
@@ -422,7 +454,7 @@ def read_tiff_region(blob_or_path, page: int, y0: int, x0: int, h: int, w: int, 
     if not 0 <= page < len(pages):
         raise ValueError("%s: page %d of a file of %d" % (name, page, len(pages)))
     pg = pages[page]
-    _check_supported(name, pg)
+    _check_supported(name, pg, float_predictor)
     if h <= 0 or w <= 0 or y0 < 0 or x0 < 0 or y0 + h > pg.height or x0 + w > pg.width:
         raise ValueError("%s: page %d: the rectangle %d x %d at (%d, %d) lies outside the image of %d x %d" % (name, page, w, h, x0, y0, pg.width, pg.height))
     if pg.bits < 8:
@@ -437,10 +469,10 @@ def read_tiff_region(blob_or_path, page: int, y0: int, x0: int, h: int, w: int, 
     return flat.reshape(pg.samples, h, w) if pg.planar == 2 else flat.reshape(h, w, pg.samples)
 
 
-def test_tiff_many(blobs_or_paths, ctx: Optional[Context] = None) -> List[Tuple[Union[int, str], str]]:
+def test_tiff_many(blobs_or_paths, ctx: Optional[Context] = None, float_predictor: bool = False) -> List[Tuple[Union[int, str], str]]:
     """[(index or path, problem)] for every file read_tiff would refuse."""
     out = []
-    for k, (src, r) in enumerate(zip(blobs_or_paths, read_tiff_many(blobs_or_paths, ctx))):
+    for k, (src, r) in enumerate(zip(blobs_or_paths, read_tiff_many(blobs_or_paths, ctx, float_predictor=float_predictor))):
         if isinstance(r, Exception):
             out.append((k if isinstance(src, (bytes, bytearray, memoryview)) else os.fspath(src), str(r)))
     return out
@@ -452,13 +484,16 @@ test_tiff_many.__test__ = False  # (not a pytest test, whatever imports it)
 def main(argv=None) -> int:
     argv = sys.argv[1:] if argv is None else list(argv)
     if len(argv) >= 2 and argv[0] == "-t":
-        files = argv[1:]
-        bad = test_tiff_many(files)
+        files = [a for a in argv[1:] if a != "--float-predictor"]
+        if not files:
+            print("usage: python -m pure_zlib_amd.tiff -t [--float-predictor] A.tif B.tif ...", file=sys.stderr)
+            return 2
+        bad = test_tiff_many(files, float_predictor="--float-predictor" in argv[1:])
         for name, why in bad:
             print("%s: %s" % (name, why))
         print("%d file(s): %s" % (len(files), "%d bad" % len(bad) if bad else "OK"))
         return 1 if bad else 0
-    print("usage: python -m pure_zlib_amd.tiff -t A.tif B.tif ...", file=sys.stderr)
+    print("usage: python -m pure_zlib_amd.tiff -t [--float-predictor] A.tif B.tif ...", file=sys.stderr)
     return 2
 
 

@@ -111,6 +111,12 @@ UNPREDICT_DESC = np.dtype([("src_off", "<u8"), ("dst_off", "<u8"), ("dst_stride"
                            ("big_endian", "u1"), ("reserved", "<u4", (3,))])
 assert UNPREDICT_DESC.itemsize == 64
 
+# pzg_unshuffle_desc (include/pzg.h) as a numpy record: one strip, tile or chunk of Context.unshuffle_many
+UNSHUFFLE_DESC = np.dtype([("src_off", "<u8"), ("dst_off", "<u8"), ("dst_stride", "<u8"), ("src_row_bytes", "<u4"), ("rows", "<u4"), ("win_row", "<u4"),
+                           ("win_rows", "<u4"), ("win_byte", "<u4"), ("win_bytes", "<u4"), ("elem_bytes", "u1"), ("sum_stride", "u1"), ("reverse", "u1"),
+                           ("reserved0", "u1"), ("reserved", "<u4", (3,))])
+assert UNSHUFFLE_DESC.itemsize == 64
+
 _STATUS_CONSTRUCTOR = {
     _ffi.E_TRUNCATED: "DecompressionError",
     _ffi.E_HDR_FCHECK: "HeaderError",
@@ -405,6 +411,32 @@ class Context:
         sync=False, and dst_base memory of the caller's own (a torch tensor's data_ptr())."""
         flags = _ffi.DEVICE_PTRS | (0 if sync else _ffi.ASYNC)
         _ffi.check(self._L.pzg_unpredict_many(self._h, src_base, src_len, dst_base, desc, status, detail or None, n, flags), self._h)
+
+    # -- the byte-plane transpose and TIFF Predictor 3 (pzg_unshuffle_many) --------------------------------
+    def unshuffle_many(self, src: np.ndarray, src_len, dst: np.ndarray, desc: np.ndarray):
+        """Thin wrapper of pzg_unshuffle_many on host numpy buffers: job i -- one strip, tile or chunk as it was decoded -- is described
+        by desc[i] (UNSHUFFLE_DESC: a structured array of pzg_unshuffle_desc), src_len[i] of its bytes are in src, and the window of
+        its reconstructed rows is delivered into dst.  Returns (status i32[n], detail u32[n,2])."""
+        desc = np.ascontiguousarray(desc)
+        if desc.dtype.itemsize != UNSHUFFLE_DESC.itemsize:
+            raise ValueError("desc: records of %d bytes (UNSHUFFLE_DESC)" % UNSHUFFLE_DESC.itemsize)
+        n = len(desc)
+        src_len = np.ascontiguousarray(src_len, dtype=np.uint64)
+        if len(src_len) != n:
+            raise ValueError("src_len: one entry per descriptor")
+        status = np.full(n, -1, dtype=np.int32)
+        detail = np.zeros((n, 2), dtype=np.uint32)
+        rc = self._L.pzg_unshuffle_many(self._h, src.ctypes.data, src_len.ctypes.data, dst.ctypes.data, desc.ctypes.data, status.ctypes.data,
+                                        detail.ctypes.data, n, 0)
+        _ffi.check(rc, self._h)
+        return status, detail
+
+    def unshuffle_many_device(self, src_base: int, src_len: int, dst_base: int, desc: int, status: int, detail: int, n: int, sync: bool = True):
+        """pzg_unshuffle_many on device memory, every pointer an integer address as unpredict_many_device takes them: the launch goes
+        on the context's stream behind what was enqueued before it, so src_len may be the out_len array of a decode enqueued with
+        sync=False."""
+        flags = _ffi.DEVICE_PTRS | (0 if sync else _ffi.ASYNC)
+        _ffi.check(self._L.pzg_unshuffle_many(self._h, src_base, src_len, dst_base, desc, status, detail or None, n, flags), self._h)
 
     def decompress_many_sharded(self, batches, sync: bool = True, gzip: bool = False, lpt: bool = False, raw: bool = False,
                                 crc32: bool = False):
