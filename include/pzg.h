@@ -95,6 +95,8 @@ extern "C" {
                             the latter, d1 = the image's pixel_bits; pzg_expand_many: only the latter, d1 = color_type << 8 | bit_depth */
 #define PZG_E_PALETTE 24  /* (0.5) pzg_expand_many only: a pixel of a palette image has an index >= pal_len; d0 = its row, d1 = its x: the
                              first such pixel in row-major order */
+#define PZG_E_LZW 25  /* (0.5) pzg_unlzw_many only: a code that is neither a literal, an entry made so far, nor the next free entry behind
+                         a previous code; d0 = the code, d1 = the bytes produced so far */
 #define PZG_E_SCAN 22  /* pzg_index_scan only: the chain of blocks did not reach the final block.
                           d0 = the status the chain's last segment met (0: a dead wave),
                           d1 = low 32 bits of that segment's start bit.
@@ -744,6 +746,44 @@ PZG_API int pzg_unshuffle_many(pzg_ctx *ctx,
         const pzg_unshuffle_desc *desc,      /* n */
         int32_t *status, uint32_t *detail,   /* detail: 2n, or NULL */
         uint32_t n, uint32_t flags);         /* 0, PZG_DEVICE_PTRS, PZG_DEVICE_PTRS | PZG_ASYNC */
+
+/*
+ * pzg_unlzw_many (0.5): EXTENSION -- LZW as TIFF (Compression 5, the post-6.0 form) and PDF (LZWDecode) pack it: n streams in one launch,
+ * one wavefront a stream.  The arrays mean what they mean in pzg_decompress_many, so out_len can be the src_len array of
+ * pzg_unpredict_many / pzg_unshuffle_many enqueued behind this call.
+ * Codes and widths:
+ *   - codes are packed most significant bit first; Clear is 256, EOI is 257, the first entry is 258;
+ *   - the table starts cleared: a stream need not begin with a Clear;
+ *   - before a code is read, let f be the next free entry: 258 after a Clear, and every code after the first one following a Clear
+ *     adds an entry;
+ *   - the code is read at the smallest width w in 9..12 with f <= (1 << w) - 1 - early_change (mode bit 0, PZG_LZW_EARLY_CHANGE:
+ *     1 for TIFF and for PDF's default, 0 for PDF's EarlyChange 0);
+ *   - entries are made up to 4095; after that the width stays 12, nothing is added, and decoding goes on.
+ * Decoding: a literal emits itself; a code c with 258 <= c < f emits its entry (the string of the code that made it plus the first
+ * byte of the code behind that one); c == f with a previous code since the Clear emits the previous string plus its own first byte;
+ * any other code is PZG_E_LZW, d0 = the code, d1 = the bytes produced so far.
+ * Decoding ends with whichever comes first:
+ *   - EOI: PZG_OK;
+ *   - out_cap[i] bytes delivered: PZG_OK -- a string that crosses the capacity is cut there, out_len[i] = out_cap[i], and what follows
+ *     in the stream is not looked at (LZW carries no end-of-data integrity and libtiff stops the same way): this is NOT
+ *     PZG_E_OUT_TOO_SMALL.  out_cap[i] == 0: PZG_OK with nothing read;
+ *   - the input runs out inside or before a code: PZG_E_TRUNCATED, out_len[i] the bytes of the complete codes (in_len[i] == 0: 0).
+ * A failed stream delivers the bytes [0, out_len[i]) it had produced.  Nothing is ever written past out_cap[i]; nothing is read but
+ * the aligned dwords that hold bytes of the stream.  detail: 2n words (d0, d1 per stream), or NULL: 0, 0 unless stated.
+ * flags: 0 -- host pointers, through the staging of the host-pointer streams with dictionaries (packed, uploaded, launched, copied
+ * back) --; PZG_DEVICE_PTRS -- the launch goes on the context's stream in call order --; PZG_DEVICE_PTRS | PZG_ASYNC.
+ * pzg_last_kernel_ms reports the launch.
+ * PZG_RC_BAD_ARG: n == 0, a null array (in_base, out_base and detail may be null where nothing needs them), any other flag, mode bits
+ * other than bit 0, a context of several devices; with host pointers also an extent that wraps and an out_cap[i] of 4 GiB or more:
+ * positions are 32-bit (with device pointers such a capacity is taken as 4 GiB - 1).
+ * NOT done: codes packed least significant bit first (GIF), a variable minimum code size, the pre-6.0 TIFF bit order.
+ */
+#define PZG_LZW_EARLY_CHANGE 1u   /* TIFF, and PDF's default; 0: PDF EarlyChange 0 */
+PZG_API int pzg_unlzw_many(pzg_ctx *ctx,
+        const uint8_t *in_base, const uint64_t *in_off, const uint64_t *in_len,
+        uint8_t *out_base, const uint64_t *out_off, const uint64_t *out_cap,
+        uint64_t *out_len, int32_t *status, uint32_t *detail,   /* detail: 2n, or NULL */
+        uint32_t n, uint32_t mode, uint32_t flags);             /* 0, PZG_DEVICE_PTRS, PZG_DEVICE_PTRS | PZG_ASYNC */
 
 /*
  * decompressIncremental / ZlibDecoder (Zlib.hs:3-8, Monad.hs:163-197; driver Deflate.hs:30-48), batched: a pzg_decoder

@@ -15,7 +15,8 @@ Only what the hot path needs lives here:
              of every colour type, expanded on the device (pzg_expand_many); read_png_batch: one (N, H, W, C) tensor
   tiff.py    Deflate-compressed TIFF files in batches: every strip and tile of every page of every file in one decode launch, Predictor 2
              undone and tiles clipped in one more (pzg_unpredict_many); read_tiff_region decodes only what covers a rectangle;
-             float_predictor=True: Predictor 3 pages (float rasters) through one pzg_unshuffle_many launch as well
+             float_predictor=True: Predictor 3 pages (float rasters) through one pzg_unshuffle_many launch as well;
+             lzw=True: LZW pages (Compression 5), their strips and tiles decoded by one pzg_unlzw_many launch
   cxx/       the same module mirror in C++ (header-only; the image stages are not mirrored)
 
 There is no CPU fallback: importing works anywhere, computing needs libpzg.so and a gfx950 device.

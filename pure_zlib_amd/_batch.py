@@ -28,14 +28,20 @@ class DeviceChain:
     """Owns the buffers of one decode launch and of the stage launches behind it on the context's stream, as torch tensors: the
     streams = [(buffer, start, length)] packed into a pinned arena and uploaded, the decode destination with the exact capacities
     dec_cap (pack(dec_cap, slack=4)), the out_len array, and a zeroed status/detail block per launch ("decode" is the chain's own).
+    codecs = [(codec, count)]: contiguous runs of streams, each run decoded by its codec's launch -- "deflate": pzg_decompress_many,
+    "lzw": pzg_unlzw_many (TIFF's early change) -- into the same destination, out_len array and "decode" block; an empty run issues
+    nothing.  None: every stream is a zlib stream.
     The caller uploads and allocates everything BEFORE decode(), which waits for torch's copies and fills, issues its stage launches
     itself with sync=False, and finish() is the one sync.  A context manager: the arena is closed on every path.  Device pointers
     are integers (data_ptr()); the tensors behind them live as long as the chain."""
 
-    def __init__(self, ctx, streams: Sequence[Tuple[bytes, int, int]], dec_cap):
+    def __init__(self, ctx, streams: Sequence[Tuple[bytes, int, int]], dec_cap, codecs: Optional[Sequence[Tuple[str, int]]] = None):
         import torch
         from .zlib import PinnedArena
         self._torch, self.ctx, self.n = torch, ctx, len(streams)
+        self._codecs = [("deflate", self.n)] if codecs is None else [(c, int(k)) for c, k in codecs]
+        if sum(k for _c, k in self._codecs) != self.n or any(c not in ("deflate", "lzw") for c, _k in self._codecs):
+            raise ValueError("codecs: runs of 'deflate' or 'lzw' streams that add up to the streams")
         self._dev = torch.device("cuda", ctx.device)
         self._keep, self._blocks = [], {}
         self.dec_cap = np.ascontiguousarray(dec_cap, dtype=np.uint64)
@@ -83,8 +89,16 @@ class DeviceChain:
     def decode(self) -> None:
         """Enqueues the decode of every stream, behind everything torch was asked to copy and fill so far."""
         self._torch.cuda.synchronize(self._dev)
-        self.ctx.decompress_many_device(self._in[0], self._in[1], self._in[2], self.dec_ptr, self.dec_off_ptr, self._dec_cap_ptr, self.out_len_ptr,
-                                        self._decode[0], self._decode[1], 0, 0, self.n, sync=False)
+        first = 0
+        for codec, count in self._codecs:
+            if count:
+                args = (self._in[0], self._in[1] + 8 * first, self._in[2] + 8 * first, self.dec_ptr, self.dec_off_ptr + 8 * first,
+                        self._dec_cap_ptr + 8 * first, self.out_len_ptr + 8 * first, self._decode[0] + 4 * first, self._decode[1] + 8 * first)
+                if codec == "lzw":
+                    self.ctx.unlzw_many_device(*args, count, early_change=True, sync=False)
+                else:
+                    self.ctx.decompress_many_device(*args, 0, 0, count, sync=False)
+            first += count
 
     def finish(self) -> Dict[str, Tuple[np.ndarray, np.ndarray]]:
         """The one sync.  {launch: (status i32[n], detail u32[n, 2])} of every result block."""

@@ -33,6 +33,7 @@ E_DICT = 20  # pzg_decompress_many_dict only (extension)
 E_SCAN = 22  # pzg_index_scan, pzg_index_scan_many only (extension): the chain of blocks did not reach the final block
 E_FILTER = 23  # pzg_unfilter_many, pzg_adam7_many only (extension): row detail[0] has the filter byte detail[1] (> 4)
 E_PALETTE = 24  # pzg_expand_many only (extension): the pixel at row detail[0], x detail[1] has an index outside the palette
+E_LZW = 25  # pzg_unlzw_many only (extension): detail[0] is a code outside the table, detail[1] the bytes produced so far
 E_SEGMENT = 21  # pzg_decompress_many_segments only (extension): the blocks do not end at end_bit
 DEC_NEED_INPUT = 101  # pzg_decoder_feed: NeedMore
 DEC_OUT_FULL = 102    # pzg_decoder_feed: this call's output room is used up
@@ -44,6 +45,7 @@ LPT_ORDER = 8  # device-pointer batches: launch the longest streams first
 HOST_PINNED = 16  # host-pointer batches in page-locked arenas (pzg_host_alloc), extents ascending: no staging, no copy-out
 RAW = 32  # extension: streams are bare RFC 1951 (no header, no trailer, nothing checked); adler[] holds the Adler-32, reported only
 CRC32 = 64  # with RAW only: adler[] holds the CRC-32 of the bytes delivered (computed on the device, checked against nothing)
+LZW_EARLY_CHANGE = 1  # pzg_unlzw_many: mode (TIFF, and PDF's default)
 PIX_RGBA8 = 0  # pzg_expand_many: out_format
 PIX_RGB8 = 1
 OPT_RING_BITS = 1
@@ -59,7 +61,7 @@ SYMBOLS = [
     "pzg_decoder_create", "pzg_decoder_create_format", "pzg_decoder_destroy", "pzg_decoder_reset", "pzg_decoder_feed", "pzg_decoder_last_feed_ms", "pzg_shutdown", "pzg_set_stream", "pzg_reset_stream", "pzg_set_option", "pzg_sync", "pzg_decompress_many", "pzg_decompress",
     "pzg_adler32", "pzg_error_message", "pzg_last_kernel_ms", "pzg_strerror", "pzg_last_error", "pzg_version",
     "pzg_index_build", "pzg_decompress_many_segments", "pzg_index_scan", "pzg_index_scan_many", "pzg_gzip_find_members", "pzg_gzip_layout",
-    "pzg_unfilter_many", "pzg_adam7_many", "pzg_expand_many", "pzg_unpredict_many", "pzg_unshuffle_many",
+    "pzg_unfilter_many", "pzg_adam7_many", "pzg_expand_many", "pzg_unpredict_many", "pzg_unshuffle_many", "pzg_unlzw_many",
 ]
 
 
@@ -175,6 +177,9 @@ def lib():
     if hasattr(L, "pzg_unshuffle_many"):
         L.pzg_unshuffle_many.argtypes = [C.c_void_p, vp, u64p, vp, vp, i32p, u32p, C.c_uint32, C.c_uint32]
         L.pzg_unshuffle_many.restype = C.c_int
+    if hasattr(L, "pzg_unlzw_many"):
+        L.pzg_unlzw_many.argtypes = [C.c_void_p, vp, u64p, u64p, vp, u64p, u64p, u64p, i32p, u32p, C.c_uint32, C.c_uint32, C.c_uint32]
+        L.pzg_unlzw_many.restype = C.c_int
     L.pzg_decompress_many_sharded.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
     L.pzg_decompress_many_sharded.restype = C.c_int
     L.pzg_decoder_create.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]

@@ -51,6 +51,7 @@
 #include "pzg_expand_kernel.h"    // (expand_kernel and its launcher; expand_core.h: its statuses, a legal geometry, the bytes of a row)
 #include "pzg_unpredict_kernel.h" // (unpredict_kernel and its launcher; unpredict_core.h: its statuses, a legal geometry, the rows inside src_len)
 #include "pzg_unshuffle_kernel.h" // (unshuffle_kernel and its launcher; unshuffle_core.h: the same of the byte-plane stage)
+#include "pzg_unlzw_kernel.h"     // (unlzw_kernel and its launcher; unlzw_core.h: its statuses)
 #include "pzg_adam7_kernel.h"     // (adam7_kernel and its launcher; adam7_core.h: its statuses, a legal geometry, an image's source extent)
 
 namespace {
@@ -1074,8 +1075,10 @@ int host_path(pzg_ctx *ctx, Shard &sh, const HostBatch &b, const uint32_t *idx, 
 
 // ---- preset dictionaries (extension): a plain synchronous path on lane 0 -- pack, upload, launch, download ----------
 // (segments of an indexed stream, pzg_decompress_many_segments: start_bit / end_bit travel along -- null otherwise)
+// (LZW streams, pzg_unlzw_many: lzw_mode points at the call's mode, there are no dictionaries -- dict_len is null -- and the launch is
+// unlzw_kernel's; the packing, the arenas and the way back are the same)
 int dict_path(pzg_ctx *ctx, Shard &sh, const HostBatch &b, const uint8_t *dict_base, const uint64_t *dict_off, const uint64_t *dict_len,
-              uint32_t n, const uint8_t *start_bit = nullptr, const uint64_t *end_bit = nullptr)
+              uint32_t n, const uint8_t *start_bit = nullptr, const uint64_t *end_bit = nullptr, const uint32_t *lzw_mode = nullptr)
 {
     std::vector<uint8_t> hmeta(96 * (size_t)n), hin, hout;  // the meta block as on the device | the packed input | the packed output
     LaneCall call(ctx, sh);
@@ -1089,8 +1092,8 @@ int dict_path(pzg_ctx *ctx, Shard &sh, const HostBatch &b, const uint8_t *dict_b
         h.in_len[i] = b.in_len[i];
         ip += pad16(b.in_len[i]);
         h.dict_off[i] = ip;
-        h.dict_len[i] = dict_len[i];
-        ip += pad16(dict_len[i]);
+        h.dict_len[i] = dict_len ? dict_len[i] : 0u;
+        ip += pad16(h.dict_len[i]);
         h.out_off[i] = op;
         h.out_cap[i] = b.out_cap[i];
         op += pad16(b.out_cap[i]);
@@ -1114,9 +1117,13 @@ int dict_path(pzg_ctx *ctx, Shard &sh, const HostBatch &b, const uint8_t *dict_b
     pzg::InflateArgs a = inflate_args(d, n, (const uint8_t *)ln.d_in[0].p, (uint8_t *)ln.d_out[0].p, start_bit != nullptr);
     a.counter = ln.d_counter;
     a.raw = raw_mode(b.flags);  // (raw streams: the dictionary is the history, whatever the stream says)
-    strip_for_launch(ctx, ln.d_strip, sh.num_cus, n, 0u, a);
+    if (!lzw_mode) strip_for_launch(ctx, ln.d_strip, sh.num_cus, n, 0u, a);
     HIP_TRY(ctx, call.begin_timed());
-    HIP_TRY(ctx, pzg::launch_inflate(a, ctx->ring_bits, sh.num_cus, st));
+    if (lzw_mode) {
+        const pzg::UnlzwArgs la{a.in_base, a.in_off, a.in_len, a.out_base, a.out_off, a.out_cap, a.out_len, a.status, a.detail, n, *lzw_mode & 1u};
+        HIP_TRY(ctx, pzg::launch_unlzw(la, st));
+    } else
+        HIP_TRY(ctx, pzg::launch_inflate(a, ctx->ring_bits, sh.num_cus, st));
     HIP_TRY(ctx, call.end_timed());
     hout.resize(op + 16);
     HIP_TRY(ctx, hipMemcpyAsync(h.out_len, d.out_len, 32 * (size_t)n, hipMemcpyDeviceToHost, st));
@@ -2143,6 +2150,27 @@ int pzg_unshuffle_many(pzg_ctx *ctx, const uint8_t *src_base, const uint64_t *sr
         pzg::launch_unshuffle,
         // the window's rows in front of the first stored row that does not lie wholly inside src_len
         [&](int32_t st, uint32_t d0, uint32_t rows, uint32_t i) { return st == PZG_OK ? rows : st == PZG_E_TRUNCATED && d0 > hd[i].win_row ? d0 - hd[i].win_row : 0u; });
+}
+
+// LZW (unlzw_core.h): the arrays of pzg_decompress_many, one wave a stream.  Device pointers: one launch on the context's stream,
+// like the image stages'.  Host pointers: the packed synchronous path of the streams with dictionaries (dict_path).
+int pzg_unlzw_many(pzg_ctx *ctx, const uint8_t *in_base, const uint64_t *in_off, const uint64_t *in_len, uint8_t *out_base, const uint64_t *out_off,
+                   const uint64_t *out_cap, uint64_t *out_len, int32_t *status, uint32_t *detail, uint32_t n, uint32_t mode, uint32_t flags)
+{
+    static_assert(pzg::Unlzw::ST_LZW == PZG_E_LZW && pzg::Unlzw::ST_TRUNCATED == PZG_E_TRUNCATED && pzg::Unlzw::ST_OK == PZG_OK, "the core's statuses are the header's");
+    if (!stage_call_ok(ctx, n, flags) || (mode & ~PZG_LZW_EARLY_CHANGE) || !in_off || !in_len || !out_off || !out_cap || !out_len || !status) return PZG_RC_BAD_ARG;
+    if (flags & PZG_DEVICE_PTRS) {
+        if (!in_base || !out_base) return PZG_RC_BAD_ARG;
+        return guarded(ctx, "pzg_unlzw_many", [&]() -> int {
+            const pzg::UnlzwArgs a{in_base, in_off, in_len, out_base, out_off, out_cap, out_len, status, detail, n, mode & PZG_LZW_EARLY_CHANGE};
+            return stream_launch(ctx, *ctx->shards[0], flags, nothing_before, [&](hipStream_t s) { return pzg::launch_unlzw(a, s); });
+        });
+    }
+    const HostBatch b{in_base, in_off, in_len, out_base, out_off, out_cap, out_len, status, detail, nullptr, nullptr, 0u};
+    if (!extents_ok(b, n)) return PZG_RC_BAD_ARG;
+    for (uint32_t i = 0; i < n; ++i)
+        if ((out_cap[i] >> 32) || (in_len[i] && !in_base)) return PZG_RC_BAD_ARG;  // (positions are 32-bit)
+    return guarded(ctx, "pzg_unlzw_many", [&]() -> int { return dict_path(ctx, *ctx->shards[0], b, nullptr, nullptr, nullptr, n, nullptr, nullptr, &mode); });
 }
 
 int pzg_decompress_many_sharded(pzg_ctx *ctx, const pzg_device_batch *batches, uint32_t nbatches, uint32_t flags)

@@ -204,6 +204,9 @@ extern "C" int pzg_error_message(const uint8_t *in, uint64_t in_len, int32_t sta
     case PZG_E_PALETTE:  // extension (pzg_expand_many)
         snprintf(buf, buf_len, "Block format error: row %u, pixel %u: palette index outside the palette", d0, d1);
         break;
+    case PZG_E_LZW:  // extension (pzg_unlzw_many)
+        snprintf(buf, buf_len, "Block format error: LZW code %u is not in the table after %u bytes", d0, d1);
+        break;
     default: snprintf(buf, buf_len, "unknown status %d", status); break;
     }
     return (int)strlen(buf);

@@ -248,6 +248,19 @@ struct UnshuffleArgs {
     uint32_t n;
 };
 
+// LZW (pzg_unlzw_kernel.h, unlzw_core.h; compiled with pzg_api.cpp): one wave a stream, the arrays those of InflateArgs.  Every
+// pointer is device memory.
+struct UnlzwArgs {
+    const uint8_t *in_base;
+    const uint64_t *in_off, *in_len;    // n
+    uint8_t *out_base;
+    const uint64_t *out_off, *out_cap;  // n
+    uint64_t *out_len;                  // n
+    int32_t *status;                    // n
+    uint32_t *detail;                   // 2n or null
+    uint32_t n, early_change;
+};
+
 // partials: 3 * 4 * ceil(max_waves / 4) uint32 of device scratch
 hipError_t launch_adler32(const uint8_t *buf, uint64_t len, uint32_t init, uint32_t *partials, uint32_t max_waves,
                           uint32_t *out, hipStream_t stream);

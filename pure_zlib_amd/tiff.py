@@ -11,20 +11,26 @@ With float_predictor=True the floating-point predictor (Predictor 3, TIFF Techni
 models and other float rasters) is read as well: the strips and tiles of such pages go through ONE pzg_unshuffle_many launch -- a
 byte-wise running sum along the row, then the byte planes transposed back into elements -- behind the pzg_unpredict_many launch of
 the others, on the same stream and with the same out_len array; a batch without such pages issues the launches it always did.
+With lzw=True LZW pages (Compression 5, the post-6.0 bit order: what scanners, Photoshop and older GDAL / libtiff defaults write) are
+read through every path a Deflate page has: their strips and tiles go to ONE pzg_unlzw_many launch beside the pzg_decompress_many
+launch of the Deflate ones, into the same decode buffer and out_len array, and the stage launches follow as before (a batch that
+holds Deflate and LZW jobs for both stages issues the Deflate launch once per stage's run).  LZW has no end-of-data check: a strip
+that ends early is "not enough image data" from the stage, a code outside the table is the decoder's own error, and a strip in the
+bit order from before TIFF 6.0 is a NotImplementedError for its file.
 
     parse_tiff(blob)                  -> [TiffPage]               (pure Python, no GPU; ValueError names the page and the tag)
     read_tiff_many(blobs_or_paths)    -> [[TiffImage per page], or the DecompressionError / ValueError / NotImplementedError of that file]
     read_tiff(blob_or_path, page=0)   -> TiffImage                (raises)
     read_tiff_region(blob_or_path, page, y0, x0, h, w) -> np.ndarray   (only the strips or tiles that cover the rectangle are decoded)
     test_tiff_many(blobs_or_paths)    -> [(index_or_name, problem)]   (empty: every file is sound)
-    python -m pure_zlib_amd.tiff -t [--float-predictor] A.tif B.tif ...
-    (each of the four readers takes float_predictor=False)
+    python -m pure_zlib_amd.tiff -t [--float-predictor] [--lzw] A.tif B.tif ...
+    (each of the four readers takes float_predictor=False and lzw=False)
 
 Byte orders II and MM, classic TIFF and BigTIFF, strips and tiles, PlanarConfiguration 1 and 2, Predictor 1 and 2, 8/16/32/64-bit
 samples of any SampleFormat, and 1/2/4-bit single-sample images as packed rows; with float_predictor=True Predictor 3 on
 16/32/64-bit floating-point samples, chunky with up to four samples or as separate planes.  `data` is the samples as the file stores
 them, in the file's byte order: PhotometricInterpretation, ExtraSamples, Orientation and ColorMap are reported, not interpreted.  Not
-done (NotImplementedError, for that file alone): any other compression, Predictor 3 (the floating-point predictor) without
+done (NotImplementedError, for that file alone): any other compression (LZW without lzw=True among them), old-style LZW, Predictor 3 (the floating-point predictor) without
 float_predictor=True, FillOrder 2, unequal BitsPerSample, bits below 8 with several samples or with Predictor 2, Predictor 2 with bits
 outside 8/16/32/64, Predictor 2 or 3 with more than four chunky samples, 24-bit floats, subsampled YCbCr, a strip or tile of 4 GiB or
 more.  Predictor 3 on samples that are not floating-point, or on 8-bit ones, is a ValueError (tags 317 / 339): libtiff refuses such
@@ -224,10 +230,14 @@ def parse_tiff(blob, name: str = "tiff") -> List[TiffPage]:
     return pages
 
 
-def _check_supported(name: str, pg: TiffPage, float_predictor: bool = False) -> None:
+def _check_supported(name: str, pg: TiffPage, float_predictor: bool = False, lzw: bool = False, blob: bytes = b"") -> None:
     where = "%s: page %d" % (name, pg.index)
-    if pg.compression not in (8, 32946):
+    if pg.compression not in (8, 32946) and not (lzw and pg.compression == 5):
         raise NotImplementedError("%s: Compression %d (only Deflate, 8 and 32946, is read)" % (where, pg.compression))
+    if pg.compression == 5:
+        for k, (o, c) in enumerate(zip(pg.offsets, pg.byte_counts)):
+            if c >= 2 and blob[o] == 0 and blob[o + 1] & 1:  # (libtiff's test: codes packed from the low bit, written before TIFF 6.0)
+                raise NotImplementedError("%s, %s %d: old-style LZW (the bit order from before TIFF 6.0) is not read" % (where, "tile" if pg.tiled else "strip", k))
     if pg.predictor == 3 and not float_predictor:
         raise NotImplementedError("%s: Predictor 3 (the floating-point predictor) is not read" % where)
     if pg.predictor not in (1, 2, 3):
@@ -302,6 +312,7 @@ class _Job:
     sample_bytes: int
     samples: int
     big_endian: bool
+    lzw: bool = False
 
 
 def _page_jobs(f: int, blob: bytes, pg: TiffPage, base: int, stride: int, plane_bytes: int, rect=None) -> List[_Job]:
@@ -323,7 +334,8 @@ def _page_jobs(f: int, blob: bytes, pg: TiffPage, base: int, stride: int, plane_
                 left, right = max(rx, b0), min(rx + rw, b0 + srb, image_rb)
                 k = plane * per_plane + ty * pg.across + tx
                 out.append(_Job(f, pg.index, k, pg.tiled, blob, pg.offsets[k], pg.byte_counts[k], srb, rows, (top - y0, bottom - top, left - b0, right - left),
-                                base + plane * plane_bytes + (top - ry) * stride + (left - rx), stride, pg.predictor, sb, s, pg.big_endian))
+                                base + plane * plane_bytes + (top - ry) * stride + (left - rx), stride, pg.predictor, sb, s, pg.big_endian,
+                                pg.compression == 5))
     return out
 
 
@@ -334,6 +346,10 @@ def _job_error(j: _Job, st: int, detail, ust: int) -> Optional[DecompressionErro
         return None
     if st == _ffi.E_OUT_TOO_SMALL:
         return DecompressionError("FormatError", where + "too much image data", _ffi.E_FILTER)
+    if j.lzw and st == _ffi.E_TRUNCATED:  # (an LZW stream that ends early has no message of its own: what counts is whether rows are missing)
+        st = _ffi.OK
+        if ust == _ffi.OK:
+            return None
     if st != _ffi.OK:
         e = error_from_status(j.blob[j.start:j.start + j.length], st, detail)
         return DecompressionError(e.constructor, where + e.message, e.status, e.detail)
@@ -348,10 +364,16 @@ def _run(ctx: Context, jobs: List[_Job], total_pix: int, out_ptr: Optional[int])
     both stages find their src_len in its out_len array; errors come back under the jobs' own indices.  Returns (the pixel buffer on
     the host or None, {job: its DecompressionError}).  out_ptr: the jobs' dst_off count from this device address and nothing is
     copied out."""
-    order = sorted(range(len(jobs)), key=lambda k: jobs[k].predictor == 3)  # (stable: file order within a kind)
+    # (stable: file order within a kind.  The LZW jobs of the two stages meet in the middle -- unpredict Deflate | unpredict LZW |
+    # unshuffle LZW | unshuffle Deflate -- so that they are ONE contiguous run and one launch)
+    order = sorted(range(len(jobs)), key=lambda k: (jobs[k].predictor == 3, jobs[k].lzw != (jobs[k].predictor == 3)))
     run = [jobs[k] for k in order]
     n = len(run)
     nu = sum(1 for j in run if j.predictor != 3)
+    lz = [j.lzw for j in run]
+    l0 = lz.index(True) if True in lz else n           # Deflate [0, l0) | LZW [l0, l1) | Deflate [l1, n)
+    l1 = n - lz[::-1].index(True) if True in lz else n
+    codecs = None if l0 == n else [("deflate", l0), ("lzw", l1 - l0), ("deflate", n - l1)]
     desc, fdesc = np.zeros(nu, dtype=UNPREDICT_DESC), np.zeros(n - nu, dtype=UNSHUFFLE_DESC)
     for d, j in zip(list(desc) + list(fdesc), run):
         d["dst_off"], d["dst_stride"], d["src_row_bytes"], d["rows"] = j.dst_off, j.dst_stride, j.srb, j.rows
@@ -360,7 +382,7 @@ def _run(ctx: Context, jobs: List[_Job], total_pix: int, out_ptr: Optional[int])
             d["elem_bytes"], d["sum_stride"], d["reverse"] = j.sample_bytes, j.samples, int(not j.big_endian)
         else:
             d["predictor"], d["sample_bytes"], d["samples"], d["big_endian"] = j.predictor, j.sample_bytes, j.samples, int(j.big_endian)
-    with DeviceChain(ctx, [(j.blob, j.start, j.length) for j in run], [j.rows * j.srb for j in run]) as ch:
+    with DeviceChain(ctx, [(j.blob, j.start, j.length) for j in run], [j.rows * j.srb for j in run], codecs) as ch:
         pix = ch.scratch(total_pix + 16) if out_ptr is None else None
         dst = out_ptr if pix is None else pix.data_ptr()
         desc["src_off"], fdesc["src_off"] = ch.dec_off[:nu], ch.dec_off[nu:]  # (job k reads its strip or tile where the decode put it)
@@ -385,7 +407,7 @@ def _named(name: str, e: DecompressionError) -> DecompressionError:
 
 
 def read_tiff_many(blobs_or_paths: Sequence[Union[str, os.PathLike, bytes, bytearray, memoryview]], ctx: Optional[Context] = None,
-                   device_out: Optional[Tuple[int, Sequence[int], Sequence[int]]] = None, float_predictor: bool = False) -> List[Union[List[TiffImage], Exception]]:
+                   device_out: Optional[Tuple[int, Sequence[int], Sequence[int]]] = None, float_predictor: bool = False, lzw: bool = False) -> List[Union[List[TiffImage], Exception]]:
     """Per file the list of its pages, or in its place the exception that read_tiff would raise for it: a bad file never disturbs its
     neighbours.  float_predictor=True: pages with Predictor 3 are read (floating-point samples of 16, 32 or 64 bits) -- their strips and
     tiles go through one pzg_unshuffle_many launch behind the pzg_unpredict_many launch of the others; without it such a page is the
@@ -402,7 +424,7 @@ def read_tiff_many(blobs_or_paths: Sequence[Union[str, os.PathLike, bytes, bytea
             name = path or name
             pages = parse_tiff(blob, name)
             for pg in pages:
-                _check_supported(name, pg, float_predictor)
+                _check_supported(name, pg, float_predictor, lzw, blob)
             places, mine = [], []
             for pg in pages:
                 rb = pg.row_bytes(pg.width)
@@ -435,9 +457,9 @@ def read_tiff_many(blobs_or_paths: Sequence[Union[str, os.PathLike, bytes, bytea
     return results
 
 
-def read_tiff(blob_or_path, page: int = 0, ctx: Optional[Context] = None, float_predictor: bool = False) -> TiffImage:
+def read_tiff(blob_or_path, page: int = 0, ctx: Optional[Context] = None, float_predictor: bool = False, lzw: bool = False) -> TiffImage:
     """One page of one file.  Raises what read_tiff_many would put in the file's place."""
-    r = read_tiff_many([blob_or_path], ctx, float_predictor=float_predictor)[0]
+    r = read_tiff_many([blob_or_path], ctx, float_predictor=float_predictor, lzw=lzw)[0]
     if isinstance(r, Exception):
         raise r
     if not 0 <= page < len(r):
@@ -445,7 +467,7 @@ def read_tiff(blob_or_path, page: int = 0, ctx: Optional[Context] = None, float_
     return r[page]
 
 
-def read_tiff_region(blob_or_path, page: int, y0: int, x0: int, h: int, w: int, ctx: Optional[Context] = None, float_predictor: bool = False) -> np.ndarray:
+def read_tiff_region(blob_or_path, page: int, y0: int, x0: int, h: int, w: int, ctx: Optional[Context] = None, float_predictor: bool = False, lzw: bool = False) -> np.ndarray:
     """The rectangle of h rows from y0 and w pixels from x0 of a page: read_tiff(...).data[y0:y0 + h, x0:x0 + w] ([:, y0:.., x0:..] of a
     PlanarConfiguration 2 page), decoding only the strips or tiles that cover it; each is clipped to the rectangle on the device."""
     path, blob = load(blob_or_path)
@@ -454,7 +476,7 @@ def read_tiff_region(blob_or_path, page: int, y0: int, x0: int, h: int, w: int, 
     if not 0 <= page < len(pages):
         raise ValueError("%s: page %d of a file of %d" % (name, page, len(pages)))
     pg = pages[page]
-    _check_supported(name, pg, float_predictor)
+    _check_supported(name, pg, float_predictor, lzw, blob)
     if h <= 0 or w <= 0 or y0 < 0 or x0 < 0 or y0 + h > pg.height or x0 + w > pg.width:
         raise ValueError("%s: page %d: the rectangle %d x %d at (%d, %d) lies outside the image of %d x %d" % (name, page, w, h, x0, y0, pg.width, pg.height))
     if pg.bits < 8:
@@ -469,10 +491,10 @@ def read_tiff_region(blob_or_path, page: int, y0: int, x0: int, h: int, w: int, 
     return flat.reshape(pg.samples, h, w) if pg.planar == 2 else flat.reshape(h, w, pg.samples)
 
 
-def test_tiff_many(blobs_or_paths, ctx: Optional[Context] = None, float_predictor: bool = False) -> List[Tuple[Union[int, str], str]]:
+def test_tiff_many(blobs_or_paths, ctx: Optional[Context] = None, float_predictor: bool = False, lzw: bool = False) -> List[Tuple[Union[int, str], str]]:
     """[(index or path, problem)] for every file read_tiff would refuse."""
     out = []
-    for k, (src, r) in enumerate(zip(blobs_or_paths, read_tiff_many(blobs_or_paths, ctx, float_predictor=float_predictor))):
+    for k, (src, r) in enumerate(zip(blobs_or_paths, read_tiff_many(blobs_or_paths, ctx, float_predictor=float_predictor, lzw=lzw))):
         if isinstance(r, Exception):
             out.append((k if isinstance(src, (bytes, bytearray, memoryview)) else os.fspath(src), str(r)))
     return out
@@ -484,16 +506,16 @@ test_tiff_many.__test__ = False  # (not a pytest test, whatever imports it)
 def main(argv=None) -> int:
     argv = sys.argv[1:] if argv is None else list(argv)
     if len(argv) >= 2 and argv[0] == "-t":
-        files = [a for a in argv[1:] if a != "--float-predictor"]
+        files = [a for a in argv[1:] if a not in ("--float-predictor", "--lzw")]
         if not files:
-            print("usage: python -m pure_zlib_amd.tiff -t [--float-predictor] A.tif B.tif ...", file=sys.stderr)
+            print("usage: python -m pure_zlib_amd.tiff -t [--float-predictor] [--lzw] A.tif B.tif ...", file=sys.stderr)
             return 2
-        bad = test_tiff_many(files, float_predictor="--float-predictor" in argv[1:])
+        bad = test_tiff_many(files, float_predictor="--float-predictor" in argv[1:], lzw="--lzw" in argv[1:])
         for name, why in bad:
             print("%s: %s" % (name, why))
         print("%d file(s): %s" % (len(files), "%d bad" % len(bad) if bad else "OK"))
         return 1 if bad else 0
-    print("usage: python -m pure_zlib_amd.tiff -t [--float-predictor] A.tif B.tif ...", file=sys.stderr)
+    print("usage: python -m pure_zlib_amd.tiff -t [--float-predictor] [--lzw] A.tif B.tif ...", file=sys.stderr)
     return 2
 
 

@@ -137,6 +137,7 @@ _STATUS_CONSTRUCTOR = {
     _ffi.E_DICT: "HeaderError",         # extension (preset dictionaries)
     _ffi.E_FILTER: "FormatError",       # extension (pzg_unfilter_many)
     _ffi.E_PALETTE: "FormatError",      # extension (pzg_expand_many)
+    _ffi.E_LZW: "FormatError",          # extension (pzg_unlzw_many)
 }
 
 
@@ -437,6 +438,31 @@ class Context:
         sync=False."""
         flags = _ffi.DEVICE_PTRS | (0 if sync else _ffi.ASYNC)
         _ffi.check(self._L.pzg_unshuffle_many(self._h, src_base, src_len, dst_base, desc, status, detail or None, n, flags), self._h)
+
+    # -- LZW streams: TIFF Compression 5, PDF LZWDecode (pzg_unlzw_many) ------------------------------------
+    def unlzw_many(self, in_buf: np.ndarray, in_off, in_len, out: np.ndarray, out_off, out_cap, early_change: bool = True):
+        """Thin wrapper of pzg_unlzw_many on host numpy buffers: stream i is in_len[i] bytes at in_buf[in_off[i]], its output goes to
+        out[out_off[i]] with room for out_cap[i].  Returns (out_len u64[n], status i32[n], detail u32[n,2])."""
+        in_off, in_len, out_off, out_cap = (np.ascontiguousarray(x, dtype=np.uint64) for x in (in_off, in_len, out_off, out_cap))
+        n = len(in_off)
+        if not (len(in_len) == len(out_off) == len(out_cap) == n):
+            raise ValueError("in_off, in_len, out_off, out_cap: one entry per stream")
+        out_len = np.zeros(n, dtype=np.uint64)
+        status = np.full(n, -1, dtype=np.int32)
+        detail = np.zeros((n, 2), dtype=np.uint32)
+        rc = self._L.pzg_unlzw_many(self._h, in_buf.ctypes.data, in_off.ctypes.data, in_len.ctypes.data, out.ctypes.data, out_off.ctypes.data,
+                                    out_cap.ctypes.data, out_len.ctypes.data, status.ctypes.data, detail.ctypes.data, n,
+                                    _ffi.LZW_EARLY_CHANGE if early_change else 0, 0)
+        _ffi.check(rc, self._h)
+        return out_len, status, detail
+
+    def unlzw_many_device(self, in_base: int, in_off: int, in_len: int, out_base: int, out_off: int, out_cap: int, out_len: int, status: int,
+                          detail: int, n: int, early_change: bool = True, sync: bool = True):
+        """pzg_unlzw_many on device memory, every pointer an integer address: the launch goes on the context's stream behind what was
+        enqueued before it, and out_len may be the src_len array of a stage enqueued behind it."""
+        flags = _ffi.DEVICE_PTRS | (0 if sync else _ffi.ASYNC)
+        _ffi.check(self._L.pzg_unlzw_many(self._h, in_base, in_off, in_len, out_base, out_off, out_cap, out_len, status, detail or None, n,
+                                          _ffi.LZW_EARLY_CHANGE if early_change else 0, flags), self._h)
 
     def decompress_many_sharded(self, batches, sync: bool = True, gzip: bool = False, lpt: bool = False, raw: bool = False,
                                 crc32: bool = False):
